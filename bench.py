@@ -19,6 +19,12 @@ Single process (N=1) by default; for N>1 the driver launches this under
 torch.distributed.run with one rank per GPU; torch.distributed (gloo) is
 used only for bootstrap (RCCL unique id exchange) and barriers — compute and
 communication run in libdistjoin.so (HIP + RCCL over xGMI).
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the steps, optionally write the last step's result (--dump-outputs DIR) and
+print the record. Everything that takes runs of its own — the CPU baseline
+leg and, at N>1, the reference-default nvlink_domain_size=1 leg — runs only
+with --full; without it those record fields are null.
 """
 import argparse
 import json
@@ -84,6 +90,47 @@ def cpu_baseline_leg(sample_rows):
     }
 
 
+DUMP_COLUMNS = ("left_key", "left_payload", "right_key", "right_payload")
+DUMP_MAX_BYTES = 64_000_000
+DUMP_SEED = 0x5EED
+
+
+def sample_output(cols, max_bytes=DUMP_MAX_BYTES, seed=DUMP_SEED):
+    """Canonical, bounded form of one rank's join result for --dump-outputs.
+
+    The join emits rows in no fixed order, so the dump must not depend on row
+    position: a result too large for `max_bytes` (as float64) is thinned by
+    keeping a row iff a seeded hash of the row's own values falls under a
+    threshold, and the kept rows are sorted lexicographically. Two runs on
+    the same inputs therefore write identical files."""
+    n = len(cols[0])
+    budget = (max_bytes - 65536) // (8 * len(cols))  # slack: .npy headers + row count
+    if n > budget:
+        h = np.full(n, seed, dtype=np.uint64)
+        for c in cols:
+            h = (h ^ np.ascontiguousarray(c).view(np.uint64)) * np.uint64(0x9E3779B97F4A7C15)
+            h ^= h >> np.uint64(29)
+        # aim 10% under the budget: the kept count is binomial, sd << 10%
+        keep = h < np.uint64(int(0.9 * budget / n * 2.0**64))
+        cols = [c[keep] for c in cols]
+    idx = np.lexsort(tuple(reversed(cols)))
+    return [c[idx][:budget] for c in cols]
+
+
+def dump_outputs(out_dir, cols, suffix=""):
+    """Write `cols` (the int64 columns a caller of the timed path receives) as
+    DIR/<name>.npy in float64, plus output_rows.npy (the full row count)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = len(cols[0])
+    for name, c in zip(DUMP_COLUMNS, sample_output(cols)):
+        # float64 holds every integer below 2^53 exactly; keys and payloads
+        # here are row indices / values below 2 * rows * N
+        assert len(c) == 0 or int(np.abs(c).max()) < 2**53, name
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), c.astype(np.float64))
+    np.save(os.path.join(out_dir, f"output_rows{suffix}.npy"),
+            np.array([total], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -101,8 +148,15 @@ def main():
     ap.add_argument("--compression", action="store_true",
                     help="cascaded (delta+bitpack) compression on the wire — config 4's "
                          "knob; rarely pays on intra-node xGMI")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the CPU "
+                         "baseline (N=1) and the nvlink_domain_size=1 alt mode (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result columns "
+                         "to DIR/<name>.npy (float64; a seeded sample if over 64 MB)")
     ap.add_argument("--cpu-baseline-rows", type=int, default=100_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -143,12 +197,14 @@ def main():
 
     nvl = args.nvlink_domain_size if args.nvlink_domain_size > 0 else N
 
-    def step(nvl_mode=None):
+    def step(nvl_mode=None, keep=False):
         t = L.dj_cpp_distributed_inner_join_i64_full(comm.ptr, bk.ptr, bp.ptr, rows,
                                                      pk.ptr, pp.ptr, rows, args.over_decom,
                                                      0, int(args.compression),
                                                      nvl if nvl_mode is None else nvl_mode)
         state["matches"] = L.dj_table_num_rows(t)
+        if keep:
+            return t
         L.dj_table_free(t)
 
     def barrier_sync():
@@ -164,8 +220,9 @@ def main():
     L.dj_timing_reset()
     barrier_sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    last = None  # the last timed step's result table, held only for --dump-outputs
+    for i in range(args.steps):
+        last = step(keep=args.dump_outputs is not None and i == args.steps - 1)
     barrier_sync()
     t1 = time.perf_counter()
     elapsed = t1 - t0
@@ -187,14 +244,18 @@ def main():
               for name, pid in dj.PHASES.items()}
     L.dj_timing_enable(0)  # the alt-mode leg below must not pollute phases
 
+    if last is not None:
+        dump_outputs(args.dump_outputs, dj.table_to_numpy(last),  # frees the table
+                     suffix=f"_rank{rank}" if world > 1 else "")
+
     # At N>1 the default mode (nvlink_domain_size = world: batched all-to-all
     # pipeline, the MI355X-native result) differs from the configuration the
     # reference's README numbers ran (its default nvlink_domain_size = 1:
     # cross-domain shuffle + local join, distributed_join.cpp:152-214). So the
-    # ratio against BASELINE.md compares like-for-like, time BOTH modes and
-    # attach the alternate one to the record.
+    # ratio against BASELINE.md compares like-for-like, --full times BOTH
+    # modes and attaches the alternate one to the record.
     alt = None
-    if N > 1 and args.nvlink_domain_size == 0:
+    if args.full and N > 1 and args.nvlink_domain_size == 0:
         alt_nvl = 1
         for _ in range(min(2, args.warmup)):
             step(alt_nvl)
@@ -276,7 +337,7 @@ def main():
         all_to_all_GBs = (est_bytes / 1e9) / (phases["comm"]["ms"] / 1e3)
 
     cpu_baseline = None
-    if rank == 0 and N == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and N == 1 and not args.no_cpu_baseline:
         log(rank, "[bench] cpu baseline leg...")
         cpu_baseline = cpu_baseline_leg(args.cpu_baseline_rows)
 
@@ -294,9 +355,10 @@ def main():
             # README.md:73-86: 0.392 s for 1.6e9 input rows on 8xV100 => 4.08e9.
             # The reference ran its default nvlink_domain_size=1, so the ratio
             # uses the like-for-like leg: the alt-mode (nvl=1) measurement when
-            # the primary ran the pipeline mode, else the primary itself.
+            # the primary ran the pipeline mode, else the primary itself. A
+            # plain run in the pipeline mode has no like-for-like leg: null.
             "vs_baseline": (((alt["value"] if alt else value) / 4.08e9)
-                            if N == 8 else None),
+                            if N == 8 and (alt or args.nvlink_domain_size > 0) else None),
             "dtype": "int64",
             "data": "synthetic",
             "config": {

@@ -46,3 +46,50 @@ def test_bench_source_emits_required_fields():
         assert f'"{k}"' in src, k
     # the timed region must be barrier+sync bracketed and MAX-reduced
     assert "barrier_sync()" in src and "ReduceOp.MAX" in src
+
+
+def test_extra_legs_are_gated_behind_full():
+    """A plain run times only the headline steps: the CPU baseline leg and the
+    N>1 alt-mode leg take runs of their own and must sit behind --full."""
+    import bench
+    src = inspect.getsource(bench.main)
+    assert '"--full"' in src and '"--dump-outputs"' in src
+    assert "if args.full and rank == 0 and N == 1 and not args.no_cpu_baseline:" in src
+    assert "if args.full and N > 1 and args.nvlink_domain_size == 0:" in src
+
+
+def test_dump_sample_is_bounded_and_order_independent(tmp_path):
+    """--dump-outputs must write the same files for the same result whatever
+    order the join emitted its rows in, and stay within its byte budget."""
+    import numpy as np
+
+    import bench
+    rng = np.random.default_rng(7)
+    n = 50_000
+    cols = [rng.integers(0, 1 << 40, n, dtype=np.int64) for _ in range(4)]
+    perm = rng.permutation(n)
+    shuffled = [c[perm] for c in cols]
+
+    # small result: every row kept, lexicographically sorted
+    full = bench.sample_output(cols)
+    assert len(full[0]) == n
+    want = np.lexsort(tuple(reversed(cols)))
+    for got, c in zip(full, cols):
+        assert (got == c[want]).all()
+    for a, b in zip(full, bench.sample_output(shuffled)):
+        assert (a == b).all()
+
+    # over budget: a strict subset of the rows, same for any row order
+    budget = 400_000
+    small = bench.sample_output(cols, max_bytes=budget)
+    assert 0 < len(small[0]) and sum(c.nbytes for c in small) <= budget
+    for a, b in zip(small, bench.sample_output(shuffled, max_bytes=budget)):
+        assert (a == b).all()
+    rows = set(zip(*[c.tolist() for c in cols]))
+    assert set(zip(*[c.tolist() for c in small])) <= rows
+
+    bench.dump_outputs(str(tmp_path), cols)
+    for name in bench.DUMP_COLUMNS:
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.dtype == np.float64 and len(a) == n
+    assert np.load(tmp_path / "output_rows.npy").tolist() == [float(n)]
