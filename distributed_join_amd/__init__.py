@@ -100,6 +100,9 @@ def lib():
                                                     i32, i32, i32, i32], vp),
             "dj_cpp_distributed_inner_join_cols_multi": ([vp, vp, i32, i64, vp, i32, i64,
                                                           vp, vp, i32, i32, i32], vp),
+            "dj_cpp_shuffle_on_cols": ([vp, vp, i32, i64, vp, i32, i32, u32, i32], vp),
+            "dj_hash_strings": ([vp, vp, i64, i64, u32, vp], None),
+            "dj_string_keys64": ([vp, vp, i64, i64, vp, i32, vp], None),
             "dj_cpp_distribute_collect_roundtrip_i64": ([vp, vp, vp, i64], vp),
             "dj_table_column_type": ([vp, i32], i32),
             "dj_table_column_chars": ([vp, i32], vp),
@@ -368,6 +371,55 @@ def cpp_distributed_inner_join_cols_multi(comm, lcols, ln, rcols, rn, left_on, r
         comm.ptr, ctypes.cast(la, ctypes.c_void_p), len(lcols), ln,
         ctypes.cast(ra, ctypes.c_void_p), len(rcols), rn,
         lon.ctypes.data, ron.ctypes.data, len(lon), over_decom, 0)
+    return table_to_numpy(t)
+
+
+def upload_strings(strings):
+    """Upload a list of bytes objects as a STRING column. Returns
+    (offsets_ptr, chars_ptr, chars_bytes) — int32 offsets[n+1] and an
+    exact-size chars buffer; caller frees both via dj_dfree."""
+    L = lib()
+    sizes = np.fromiter((len(s) for s in strings), dtype=np.int64, count=len(strings))
+    off = np.zeros(len(strings) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=off[1:])
+    if off[-1] >= 2 ** 31:
+        raise ValueError("STRING column chars exceed 2^31 (int32 offsets)")
+    off32 = off.astype(np.int32)
+    chars = np.frombuffer(b"".join(strings), dtype=np.uint8)
+    d_off = L.dj_dmalloc(off32.nbytes)
+    L.dj_memcpy_h2d(d_off, off32.ctypes.data, off32.nbytes)
+    d_chars = L.dj_dmalloc(max(len(chars), 1))
+    if len(chars):
+        L.dj_memcpy_h2d(d_chars, chars.ctypes.data, len(chars))
+    return d_off, d_chars, int(len(chars))
+
+
+def hash_strings(offsets_ptr, chars_ptr, chars_bytes, n, seed=0):
+    """MurmurHash3_x86_32(row bytes, seed) per row of a device STRING column,
+    through the kernel that hashes STRING key columns. Returns uint32[n]."""
+    L = lib()
+    out = np.empty(n, dtype=np.uint32)
+    d_out = L.dj_dmalloc(max(n, 1) * 4)
+    L.dj_hash_strings(offsets_ptr, chars_ptr, chars_bytes, n, seed, d_out)
+    if n:
+        L.dj_memcpy_d2h(out.ctypes.data, d_out, n * 4)
+    L.dj_dfree(d_out)
+    return out
+
+
+def cpp_shuffle_on_cols(comm, cols, n, on, hash_fn=HASH_MURMUR3, seed=0, compression=False):
+    """shuffle_on over column descriptors (see cpp_distributed_inner_join_cols);
+    `on` lists the key column indices, STRING columns included."""
+    arr = (ColDesc * len(cols))()
+    for i, c in enumerate(cols):
+        arr[i].type_id = c[0]
+        arr[i].data = c[1]
+        arr[i].chars = c[2] if len(c) > 2 else None
+        arr[i].chars_bytes = c[3] if len(c) > 3 else 0
+    keys = np.asarray(on, dtype=np.int32)
+    t = lib().dj_cpp_shuffle_on_cols(comm.ptr, ctypes.cast(arr, ctypes.c_void_p), len(cols), n,
+                                     keys.ctypes.data, len(keys), hash_fn, seed,
+                                     int(bool(compression)))
     return table_to_numpy(t)
 
 

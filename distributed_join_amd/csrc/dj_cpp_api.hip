@@ -200,7 +200,18 @@ __global__ void fuse_keys_kernel(const int64_t* __restrict__ c0, const int64_t* 
   }
 }
 
-/* -> DBuf of n fused int64 keys for the given key columns (<= 4, int-rep) */
+bool is_string(cudf::column_view col) { return col.type().id() == cudf::type_id::STRING; }
+
+bool any_string_key(cudf::table_view t, std::vector<cudf::size_type> const& on)
+{
+  for (auto c : on)
+    if (is_string(t.column(c))) return true;
+  return false;
+}
+
+/* -> DBuf of n fused int64 keys for the given key columns (<= 4; integer-rep
+ * or STRING). A STRING column enters the chain as its dj_string_key64 row
+ * hash (dj_strhash.h), computed into a temporary 64-bit column. */
 DBuf fuse_keys(cudf::table_view t, std::vector<cudf::size_type> const& on, hipStream_t st)
 {
   const int64_t n = t.num_rows();
@@ -208,10 +219,19 @@ DBuf fuse_keys(cudf::table_view t, std::vector<cudf::size_type> const& on, hipSt
                  "multi-column join keys: 1..4 key columns supported");
   const int64_t* ptrs[4] = {nullptr, nullptr, nullptr, nullptr};
   uint32_t wide = 0;
+  std::vector<DBuf> str_keys;
   for (size_t c = 0; c < on.size(); c++) {
     cudf::column_view col = t.column(on[c]);
+    if (is_string(col)) {
+      str_keys.emplace_back((size_t)(n > 0 ? n : 1) * 8);
+      dj::hash_strings(col.head<int32_t>(), (const uint8_t*)col.chars(), n,
+                       (uint64_t*)str_keys.back().p, st);
+      ptrs[c] = str_keys.back().i64();
+      wide |= 1u << c;
+      continue;
+    }
     DJ_CHECK_ERROR(cudf::is_rep_int64(col.type()) || cudf::is_rep_int32(col.type()),
-                   "multi-column join keys must be integer-rep columns");
+                   "join/shuffle key columns must be integer-rep or STRING columns");
     ptrs[c] = col.head<int64_t>();
     if (cudf::is_rep_int64(col.type())) wide |= 1u << c;
   }
@@ -221,6 +241,8 @@ DBuf fuse_keys(cudf::table_view t, std::vector<cudf::size_type> const& on, hipSt
     hipLaunchKernelGGL(fuse_keys_kernel, dim3(grid_for_n(n)), dim3(kBlock), 0, st, ptrs[0],
                        ptrs[1], ptrs[2], ptrs[3], wide, (int)on.size(), n, weak, out.i64());
     DJ_HIP_CALL(hipGetLastError());
+    /* the row-hash temporaries go back to the pool on return */
+    if (!str_keys.empty()) DJ_HIP_CALL(hipStreamSynchronize(st));
   }
   return out;
 }
@@ -316,6 +338,8 @@ column::column(size_type size, int64_t chars_bytes)
   : _type(data_type(type_id::STRING)), _size(size), _chars_size(chars_bytes)
 {
   _data = pool_alloc(((size_t)size + 1) * sizeof(int32_t));
+  /* an empty STRING column is complete as built: offsets = {0} */
+  if (size == 0) DJ_HIP_CALL(hipMemset(_data, 0, sizeof(int32_t)));
   if (chars_bytes) _chars = pool_alloc((size_t)chars_bytes);
 }
 
@@ -844,6 +868,12 @@ AllToAllCommunicator::AllToAllCommunicator(
       }
     }
     auto col = input_table.column(c);
+    /* row sizes first: launch_communication copies the self slice of them on
+     * the COMM stream, which is not ordered after this compute-stream
+     * kernel — the stream syncs of the boundary reads below complete it
+     * before the constructor returns */
+    DBuf sizes((size_t)(n > 0 ? n : 1) * 4);
+    dj::sizes_from_offsets(col.head<int32_t>(), n, (int32_t*)sizes.p, st);
     /* char offsets at the G+1 send row boundaries */
     std::vector<int64_t> soff(G + 1);
     for (int k = 0; k <= G; k++) {
@@ -860,8 +890,6 @@ AllToAllCommunicator::AllToAllCommunicator(
      * cuDF 0.19; the receiver-side scan would otherwise wrap) */
     DJ_CHECK_ERROR(roff.empty() || roff.back() <= (int64_t)INT32_MAX,
                    "all-to-all: received string chars exceed 2^31 (int32 offsets limit)");
-    DBuf sizes((size_t)(n > 0 ? n : 1) * 4);
-    dj::sizes_from_offsets(col.head<int32_t>(), n, (int32_t*)sizes.p, st);
     strings->send_char_offsets.push_back(std::move(soff));
     strings->recv_char_offsets.push_back(std::move(roff));
     strings->sizes_to_send.push_back(std::move(sizes));
@@ -1453,7 +1481,16 @@ std::unique_ptr<cudf::table> local_inner_join_multi(cudf::table_view left,
                                                     std::vector<cudf::size_type> const& ron)
 {
   DJ_CHECK_ERROR(lon.size() == ron.size(), "left_on/right_on must have equal length");
-  if (lon.size() == 1) return local_inner_join(left, right, lon[0], ron[0]);
+  /* STRING keys (even a single one) join on the fused chain too: the row
+   * hash stands in for the string, the filter compares the real bytes, and
+   * the key STRING columns are gathered into the output on both sides */
+  bool str_keys = false;
+  for (size_t c = 0; c < lon.size(); c++) {
+    const bool ls = is_string(left.column(lon[c])), rs = is_string(right.column(ron[c]));
+    DJ_CHECK_ERROR(ls == rs, "a STRING key column must pair with a STRING key column");
+    str_keys |= ls;
+  }
+  if (lon.size() == 1 && !str_keys) return local_inner_join(left, right, lon[0], ron[0]);
   hipStream_t st = dj_rt_stream();
   const int64_t ln = left.num_rows(), rn = right.num_rows();
   const cudf::size_type ncl = left.num_columns(), ncr = right.num_columns();
@@ -1507,7 +1544,24 @@ std::unique_ptr<cudf::table> local_inner_join_multi(cudf::table_view left,
     DBuf li2((size_t)std::max<int64_t>(nout, 1) * 8);
     DBuf ri2((size_t)std::max<int64_t>(nout, 1) * 8);
     DJ_HIP_CALL(hipMemsetAsync(d_cnt.p, 0, 8, st));
-    if (nout > 0) {
+    if (nout > 0 && str_keys) {
+      dj::TupleKeys tk{};
+      tk.nk = (int)lon.size();
+      auto desc = [](cudf::column_view col) {
+        dj::TupleKeyCol d{};
+        d.data = col.head<void>();
+        d.chars = (const uint8_t*)col.chars();
+        d.kind = is_string(col) ? dj::kKeyStr
+                                : cudf::is_rep_int64(col.type()) ? dj::kKeyI64 : dj::kKeyI32;
+        return d;
+      };
+      for (size_t c = 0; c < lon.size(); c++) {
+        tk.l[c] = desc(left.column(lon[c]));
+        tk.r[c] = desc(right.column(ron[c]));
+      }
+      dj::filter_tuple_matches_mixed(tk, o1.i64(), o3.i64(), nout, li2.i64(), ri2.i64(),
+                                     (unsigned long long*)d_cnt.p, st);
+    } else if (nout > 0) {
       hipLaunchKernelGGL(filter_tuple_matches_kernel, dim3(grid_for_n(nout)), dim3(kBlock),
                          0, st, lptr[0], lptr[1], lptr[2], lptr[3], rptr[0], rptr[1],
                          rptr[2], rptr[3], lwide, rwide, (int)lon.size(), o1.i64(), o3.i64(),
@@ -1894,6 +1948,9 @@ std::unique_ptr<cudf::table> distributed_inner_join(
   DJ_CHECK_ERROR(left_on.size() <= 4, "up to 4 join key columns supported");
   validate_compression(left_compression_options);
   validate_compression(right_compression_options);
+  /* composite keys and any STRING key join on the fused key chain */
+  const bool fused_keys = left_on.size() > 1 || any_string_key(left, left_on) ||
+                          any_string_key(right, right_on);
 
   const int world = communicator->mpi_size;
   const int nvl = get_nvl_partition_size(world, nvlink_domain_size < 1 ? 1 : nvlink_domain_size);
@@ -1916,15 +1973,15 @@ std::unique_ptr<cudf::table> distributed_inner_join(
     right = r_ib->view();
   }
   if (nvl == 1) {
-    if (left_on.size() > 1) return local_inner_join_multi(left, right, left_on, right_on);
+    if (fused_keys) return local_inner_join_multi(left, right, left_on, right_on);
     return local_inner_join(left, right, left_on[0], right_on[0]);
   }
 
-  if (left_on.size() > 1) {
-    /* multi-column keys take the shuffle + local-join route (placement on
-     * the fused key chain both sides, collisions filtered in the local
-     * join); the batched od pipeline stays single-key — the hot shape the
-     * reference benchmarks */
+  if (fused_keys) {
+    /* multi-column keys, and STRING keys even alone, take the shuffle +
+     * local-join route (placement on the fused key chain both sides,
+     * collisions filtered in the local join); the batched od pipeline stays
+     * single-integer-key — the hot shape the reference benchmarks */
     CommunicationGroup g2(nvl, 1, communicator->mpi_rank);
     auto ls = shuffle_on(left, left_on, g2, communicator, left_compression_options,
                          cudf::hash_id::HASH_MURMUR3, DJ_SEED_INTRA, report_timing,
@@ -2197,10 +2254,16 @@ std::unique_ptr<cudf::table> shuffle_on(cudf::table_view const& input,
   DJ_CHECK_ERROR(on_columns.size() >= 1, "shuffle_on: at least one key column");
   const int hash_fn =
     hash_function == cudf::hash_id::HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3;
-  /* multi-column keys: placement on the fused key chain (our spec —
-   * MurmurHash3 placement is parity-unpinned) */
+  DJ_CHECK_ERROR(on_columns.size() <= 4, "shuffle_on: up to 4 key columns supported");
+  /* multi-column keys, and any STRING key: placement on the fused key chain
+   * (our spec, dj_hash.h — MurmurHash3 placement is parity-unpinned,
+   * SURVEY.md §8c) */
   DBuf fused;
-  if (on_columns.size() > 1) {
+  const bool str_key = any_string_key(input, on_columns);
+  if (on_columns.size() > 1 || str_key) {
+    DJ_CHECK_ERROR(hash_fn != DJ_HASH_IDENTITY || !str_key,
+                   "identity-hash shuffle is not defined for STRING key columns "
+                   "(cuDF has no identity hash for strings either); use HASH_MURMUR3");
     DJ_CHECK_ERROR(hash_fn != DJ_HASH_IDENTITY,
                    "identity-hash shuffle requires a single key column");
     fused = fuse_keys(input, on_columns, dj_rt_stream());
@@ -2571,13 +2634,9 @@ void* dj_cpp_distributed_inner_join_i64str(void* comm, const int64_t* d_lk,
 
 /* generic column-descriptor join (e.g. the TPC-H lineitem x orders shape:
  * int64 key + string payload on one side, int64 key + int64 payload on the
- * other). type_id: 2=INT32, 3=INT64, 4=STRING (cudf::type_id values). */
-typedef struct {
-  int type_id;
-  const void* data;  /* fixed-width data, or int32 offsets for STRING */
-  const void* chars;
-  int64_t chars_bytes;
-} dj_col_desc;
+ * other). dj_col_desc: include/distributed_join.h; type_id: 2=INT32,
+ * 3=INT64, 4=STRING (cudf::type_id values). Key indices may name STRING
+ * columns. */
 
 void* dj_cpp_distributed_inner_join_cols(void* comm, const dj_col_desc* lcols, int nl,
                                          int64_t ln, const dj_col_desc* rcols, int nr,
@@ -2638,6 +2697,74 @@ void* dj_cpp_distributed_inner_join_cols_multi(void* comm, const dj_col_desc* lc
   auto result = distributed_inner_join(left, right, lo, ro, (Communicator*)comm, lopts,
                                        ropts, over_decom, report_timing != 0, nullptr, 1);
   return result.release();
+}
+
+/* shuffle_on over column descriptors; `on` names nkeys key columns, STRING
+ * ones included (placement on the fused key chain, dj_hash.h) */
+void* dj_cpp_shuffle_on_cols(void* comm, const dj_col_desc* cols, int nc, int64_t n,
+                             const int32_t* on, int nkeys, int hash_function, uint32_t seed,
+                             int compression)
+{
+  using cudf::column_view;
+  using cudf::data_type;
+  using cudf::type_id;
+  std::vector<column_view> v;
+  for (int c = 0; c < nc; c++) {
+    if ((type_id)cols[c].type_id == type_id::STRING)
+      v.emplace_back(data_type(type_id::STRING), (cudf::size_type)n, cols[c].data,
+                     cols[c].chars, cols[c].chars_bytes);
+    else
+      v.emplace_back(data_type((type_id)cols[c].type_id), (cudf::size_type)n, cols[c].data);
+  }
+  cudf::table_view input(v);
+  std::vector<cudf::size_type> keys(on, on + nkeys);
+  auto opts = generate_compression_options_distributed(input, compression != 0);
+  auto result =
+    shuffle_on(input, keys, (Communicator*)comm, opts,
+               hash_function == DJ_HASH_IDENTITY ? cudf::hash_id::HASH_IDENTITY
+                                                 : cudf::hash_id::HASH_MURMUR3,
+               seed, false, nullptr);
+  return result.release();
+}
+
+/* test hook: d_out[i] = dj_murmur3_bytes(row i, seed) through the STRING-key
+ * row-hash kernel (its staged and direct paths, selected per block as in
+ * production). Host-synchronous. */
+void dj_hash_strings(const void* d_offsets, const void* d_chars, int64_t chars_bytes, int64_t n,
+                     uint32_t seed, uint32_t* d_out)
+{
+  hipStream_t st = dj_rt_stream();
+  /* an empty chars buffer is never dereferenced; drop the pointer so a stale
+   * one cannot be */
+  if (chars_bytes <= 0) d_chars = nullptr;
+  dj::hash_strings_seeded((const int32_t*)d_offsets, (const uint8_t*)d_chars, n, seed, d_out,
+                          st);
+  DJ_HIP_CALL(hipStreamSynchronize(st));
+}
+
+/* d_out[i] = dj_string_key64(row i): what a STRING key column contributes to
+ * the fused key chain. Launches the kernel `reps` times, each between a
+ * hipEvent pair; h_ms (host double[reps], may be NULL) receives the
+ * per-launch milliseconds (benchmark/string_key_bench.py). Host-synchronous. */
+void dj_string_keys64(const void* d_offsets, const void* d_chars, int64_t chars_bytes,
+                      int64_t n, uint64_t* d_out, int reps, double* h_ms)
+{
+  hipStream_t st = dj_rt_stream();
+  if (chars_bytes <= 0) d_chars = nullptr;
+  hipEvent_t e0, e1;
+  DJ_HIP_CALL(hipEventCreate(&e0));
+  DJ_HIP_CALL(hipEventCreate(&e1));
+  for (int r = 0; r < (reps > 0 ? reps : 1); r++) {
+    DJ_HIP_CALL(hipEventRecord(e0, st));
+    dj::hash_strings((const int32_t*)d_offsets, (const uint8_t*)d_chars, n, d_out, st);
+    DJ_HIP_CALL(hipEventRecord(e1, st));
+    DJ_HIP_CALL(hipEventSynchronize(e1));
+    float ms = 0.f;
+    DJ_HIP_CALL(hipEventElapsedTime(&ms, e0, e1));
+    if (h_ms) h_ms[r] = ms;
+  }
+  DJ_HIP_CALL(hipEventDestroy(e0));
+  DJ_HIP_CALL(hipEventDestroy(e1));
 }
 
 /* behavior hook for the parity tests: distribute a 2-column int64 table

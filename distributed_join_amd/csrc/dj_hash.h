@@ -18,6 +18,19 @@
  * with the oracle does not depend on this choice; shuffle placement parity is
  * pinned to THIS spec by our own tests.
  *
+ * STRING and composite keys (our spec, parity-unpinned like the above): the
+ * key tuple is fused into one 64-bit value by the chain
+ *
+ *   h = 0x9e3779b97f4a7c15;  for each key column c:  h = dj_mix64(h ^ v_c)
+ *
+ * where v_c is the integer value of an INT32/INT64-rep column (sign-extended)
+ * and dj_string_key64(row bytes) of a STRING column (dj_strhash.h: two
+ * MurmurHash3_x86_32 halves, seeds 0 and 0x9747B28C). Placement is then
+ * dj_murmur3_int64(fused, seed) % nparts, exactly as for an int64 key. A
+ * single STRING key takes the same chain. The join matches on the fused
+ * value and drops collisions by comparing the real columns (strings: length,
+ * then bytes). HASH_IDENTITY has no STRING form (cuDF has none either).
+ *
  * Plain C99; compiles under gcc/g++/hipcc.
  */
 #ifndef DJ_HASH_H

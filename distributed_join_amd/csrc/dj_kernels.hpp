@@ -189,6 +189,31 @@ void gather_chars_from_starts(const uint8_t* d_src_chars, const int32_t* d_start
                               const int32_t* d_dst_off, uint8_t* d_dst_chars, hipStream_t s);
 void gather_sizes(const int32_t* d_src_off, const int64_t* d_idx, int64_t n, int32_t* d_sizes,
                   hipStream_t s);
+/* STRING key columns (dj_strhash.h spec): d_out[i] = dj_string_key64 of row
+ * i. Reads offsets[0..n] and exactly the chars bytes the rows cover. */
+void hash_strings(const int32_t* d_offsets, const uint8_t* d_chars, int64_t n, uint64_t* d_out,
+                  hipStream_t s);
+/* same kernel, d_out[i] = dj_murmur3_bytes(row i, seed) (test hook) */
+void hash_strings_seeded(const int32_t* d_offsets, const uint8_t* d_chars, int64_t n,
+                         uint32_t seed, uint32_t* d_out, hipStream_t s);
+/* collision filter over key tuples with STRING columns: keep the (li, ri)
+ * pairs whose key tuples are equal column by column (strings: length, then
+ * bytes); appends to d_out_li/d_out_ri at positions drawn from *d_count
+ * (caller-zeroed), order unspecified. Per column and side: kind, data
+ * (values, or int32 offsets for kKeyStr) and chars (kKeyStr only). */
+enum { kKeyI32 = 0, kKeyI64 = 1, kKeyStr = 2 };
+struct TupleKeyCol {
+  const void* data;
+  const uint8_t* chars;
+  int kind;
+};
+struct TupleKeys {
+  TupleKeyCol l[4], r[4];
+  int nk;
+};
+void filter_tuple_matches_mixed(const TupleKeys& keys, const int64_t* d_li, const int64_t* d_ri,
+                                int64_t n, int64_t* d_out_li, int64_t* d_out_ri,
+                                unsigned long long* d_count, hipStream_t s);
 void make_test_string_sizes(const int64_t* d_keys, int64_t n, int32_t* d_sizes, hipStream_t s);
 void fill_test_strings(const int64_t* d_keys, int64_t n, const int32_t* d_offsets,
                        uint8_t* d_chars, hipStream_t s);

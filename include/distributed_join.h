@@ -161,6 +161,41 @@ int dj_rccl_selftest(int64_t n);
 int64_t dj_compress_roundtrip(const void* d_in, int64_t count, int elem_size, int num_rles,
                               int num_deltas, int use_bp, void* d_out);
 
+/* ---------------- column descriptors + STRING key columns.
+ * A column handed over the C ABI: type_id is a cudf::type_id value (2=INT32,
+ * 3=INT64, 4=STRING, ...); data is the fixed-width device array, or the
+ * int32 offsets[n+1] of a STRING column whose bytes are chars[0..chars_bytes).
+ * The descriptor joins/shuffles take key indices that may name STRING
+ * columns, alone or among up to 4 key columns (reference: arbitrary
+ * left_on/right_on/on_columns forwarded to cudf::hash_partition and
+ * cudf::inner_join, distributed_join.cpp:71-132, shuffle_on.cpp:59-60).
+ * Placement spec: csrc/dj_hash.h "STRING and composite keys". */
+typedef struct {
+  int type_id;
+  const void* data;
+  const void* chars;
+  int64_t chars_bytes;
+} dj_col_desc;
+
+/* shuffle_on over nc column descriptors of n rows; `on` holds nkeys key
+ * column indices. Returns an opaque table (this rank's rows after the
+ * shuffle). HASH_IDENTITY with a STRING key column is a loud error. */
+void* dj_cpp_shuffle_on_cols(void* comm, const dj_col_desc* cols, int nc, int64_t n,
+                             const int32_t* on, int nkeys, int hash_function, uint32_t seed,
+                             int compression);
+/* test hook: d_out[i] = MurmurHash3_x86_32(bytes of row i, seed) for a
+ * STRING column of n rows, through the same kernel (LDS-staged and direct
+ * paths) that hashes STRING key columns. Reads no byte outside
+ * [d_chars, d_chars + chars_bytes). Synchronizes. */
+void dj_hash_strings(const void* d_offsets, const void* d_chars, int64_t chars_bytes, int64_t n,
+                     uint32_t seed, uint32_t* d_out);
+/* d_out[i] = the 64-bit key a STRING row contributes to the fused key chain
+ * (csrc/dj_strhash.h). Runs `reps` launches and writes each launch's
+ * hipEvent milliseconds to h_ms (host double[reps]; may be NULL).
+ * Synchronizes. */
+void dj_string_keys64(const void* d_offsets, const void* d_chars, int64_t chars_bytes,
+                      int64_t n, uint64_t* d_out, int reps, double* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,11 +33,15 @@
 #include <memory>
 #include <vector>
 
-/* vs the reference signature below: up to 4 integer-rep key columns are
- * supported (composite keys join on a fused key chain with a post-join
- * collision filter and take the shuffle + local-join route); STRING key
- * columns throw. nparts = join-group size x over_decom_factor caps at
- * 1024. See INTEGRATION.md "Known restrictions". */
+/* vs the reference signature below: up to 4 key columns are supported, each
+ * integer-rep or STRING (a STRING key pairs with a STRING key). Composite
+ * keys, and a STRING key even alone, join on a fused key chain — a STRING
+ * row enters as the 64-bit hash of its bytes — with a post-join filter that
+ * compares the real columns byte for byte, and take the shuffle +
+ * local-join route (over_decom_factor is accepted there and has no effect).
+ * The key columns, STRING ones included, appear in the output on both
+ * sides. nparts = join-group size x over_decom_factor caps at 1024. See
+ * INTEGRATION.md "Known restrictions". */
 std::unique_ptr<cudf::table> distributed_inner_join(
   cudf::table_view left,
   cudf::table_view right,

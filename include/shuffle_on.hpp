@@ -5,6 +5,11 @@
  * int64 key bytes / identity truncation) — the reference pins identity-hash
  * placement only (test_shuffle_on.cpp:78-83); MurmurHash3 placement is
  * pinned to our documented spec.
+ * on_columns may name up to 4 columns, integer-rep or STRING. More than one
+ * column, or any STRING column, places rows by the fused key chain of
+ * dj_hash.h ("STRING and composite keys"): equal key tuples land on the same
+ * rank. HASH_IDENTITY needs a single integer-rep key column; with a STRING
+ * key it is a loud error (cuDF has no identity hash for strings either).
  */
 #pragma once
 
