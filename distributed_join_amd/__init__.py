@@ -26,6 +26,10 @@ PHASES = {
     "bucket_count": 9, "bucket_scan": 10, "bucket_scatter": 11, "join_fused": 12,
 }
 
+# output assembly (table gather + key narrowing); kept out of PHASES, whose
+# key set is part of bench.py's record
+PHASE_GATHER = 13
+
 _lib = None
 
 
@@ -111,6 +115,8 @@ def lib():
             "dj_table_num_columns": ([vp], i32),
             "dj_table_column_data": ([vp, i32], vp),
             "dj_table_free": ([vp], None),
+            "dj_gather_columns": ([vp, i32, vp, i64, i32, i32, vp], None),
+            "dj_cpp_partition_cols": ([vp, i32, i64, vp, i32, i32, i32, u32, vp], vp),
         }
         for name, (argtypes, restype) in sigs.items():
             f = getattr(_lib, name)
@@ -247,12 +253,87 @@ TYPE_TIMESTAMP_DAYS, TYPE_TIMESTAMP_S, TYPE_TIMESTAMP_MS = 5, 6, 7
 TYPE_TIMESTAMP_US, TYPE_TIMESTAMP_NS = 8, 9
 TYPE_DURATION_DAYS, TYPE_DURATION_S, TYPE_DURATION_MS = 10, 11, 12
 TYPE_DURATION_US, TYPE_DURATION_NS = 13, 14
+# appended fixed-width types (ids 0..14 above are C-ABI values and never move)
+TYPE_INT16, TYPE_UINT8, TYPE_UINT16, TYPE_UINT32 = 15, 16, 17, 18
+TYPE_UINT64, TYPE_FLOAT32, TYPE_FLOAT64, TYPE_BOOL8 = 19, 20, 21, 22
+
+# type_id -> numpy dtype of every fixed-width column type (chrono types as
+# their integer rep, BOOL8 as its one-byte rep)
+NUMPY_DTYPE = {
+    TYPE_INT8: np.dtype(np.int8), TYPE_INT32: np.dtype(np.int32),
+    TYPE_INT64: np.dtype(np.int64),
+    TYPE_TIMESTAMP_DAYS: np.dtype(np.int32), TYPE_TIMESTAMP_S: np.dtype(np.int64),
+    TYPE_TIMESTAMP_MS: np.dtype(np.int64), TYPE_TIMESTAMP_US: np.dtype(np.int64),
+    TYPE_TIMESTAMP_NS: np.dtype(np.int64),
+    TYPE_DURATION_DAYS: np.dtype(np.int32), TYPE_DURATION_S: np.dtype(np.int64),
+    TYPE_DURATION_MS: np.dtype(np.int64), TYPE_DURATION_US: np.dtype(np.int64),
+    TYPE_DURATION_NS: np.dtype(np.int64),
+    TYPE_INT16: np.dtype(np.int16), TYPE_UINT8: np.dtype(np.uint8),
+    TYPE_UINT16: np.dtype(np.uint16), TYPE_UINT32: np.dtype(np.uint32),
+    TYPE_UINT64: np.dtype(np.uint64), TYPE_FLOAT32: np.dtype(np.float32),
+    TYPE_FLOAT64: np.dtype(np.float64), TYPE_BOOL8: np.dtype(np.uint8),
+}
+# default type_id of a numpy dtype (uint8 -> UINT8; pass TYPE_BOOL8 explicitly)
+_TYPE_OF_DTYPE = {
+    np.dtype(np.int8): TYPE_INT8, np.dtype(np.int16): TYPE_INT16,
+    np.dtype(np.int32): TYPE_INT32, np.dtype(np.int64): TYPE_INT64,
+    np.dtype(np.uint8): TYPE_UINT8, np.dtype(np.uint16): TYPE_UINT16,
+    np.dtype(np.uint32): TYPE_UINT32, np.dtype(np.uint64): TYPE_UINT64,
+    np.dtype(np.float32): TYPE_FLOAT32, np.dtype(np.float64): TYPE_FLOAT64,
+    np.dtype(np.bool_): TYPE_BOOL8,
+}
+
+
+class DeviceColumn:
+    """Owning device copy of a numpy array of any supported fixed-width dtype.
+    `desc` is the (type_id, data_ptr) tuple the *_cols entry points take.
+    offset_elems > 0 places the column that many elements into its allocation
+    (an element-aligned, not allocation-aligned, base)."""
+
+    def __init__(self, a, type_id=None, offset_elems=0):
+        a = np.ascontiguousarray(a)
+        if type_id is None:
+            if a.dtype not in _TYPE_OF_DTYPE:
+                raise TypeError(f"unsupported column dtype {a.dtype}")
+            type_id = _TYPE_OF_DTYPE[a.dtype]
+        want = NUMPY_DTYPE[type_id]
+        if a.dtype.itemsize != want.itemsize:
+            raise TypeError(f"dtype {a.dtype} does not fit type_id {type_id} ({want})")
+        self.type_id = int(type_id)
+        self.n = len(a)
+        self.itemsize = a.dtype.itemsize
+        off = int(offset_elems) * self.itemsize
+        self.base = lib().dj_dmalloc(max(a.nbytes + off, 1))
+        self.ptr = self.base + off
+        if a.nbytes:
+            lib().dj_memcpy_h2d(self.ptr, a.ctypes.data, a.nbytes)
+
+    @property
+    def desc(self):
+        return (self.type_id, self.ptr)
+
+    def free(self):
+        if self.base:
+            lib().dj_dfree(self.base)
+            self.base = None
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def upload_column(a, type_id=None):
+    """Upload a numpy array of any supported dtype; returns a DeviceColumn."""
+    return DeviceColumn(a, type_id)
 
 
 def table_to_numpy(tbl_ptr):
     """Copy an opaque cudf::table* (C ABI) into numpy columns and free it.
-    Fixed-width columns -> int64/int32 arrays; STRING columns ->
-    (offsets int32 array, chars uint8 array) tuples."""
+    Fixed-width columns -> arrays of their own dtype (NUMPY_DTYPE); STRING
+    columns -> (offsets int32 array, chars uint8 array) tuples."""
     L = lib()
     n = L.dj_table_num_rows(tbl_ptr)
     ncols = L.dj_table_num_columns(tbl_ptr)
@@ -268,15 +349,10 @@ def table_to_numpy(tbl_ptr):
             if nch:
                 L.dj_memcpy_d2h(ch.ctypes.data, L.dj_table_column_chars(tbl_ptr, c), nch)
             cols.append((off, ch[:nch]))
-        elif t in (TYPE_INT32, TYPE_TIMESTAMP_DAYS, TYPE_DURATION_DAYS):
-            out = np.empty(n, dtype=np.int32)
-            if n:
-                L.dj_memcpy_d2h(out.ctypes.data, data, n * 4)
-            cols.append(out)
         else:
-            out = np.empty(n, dtype=np.int64)
+            out = np.empty(n, dtype=NUMPY_DTYPE[t])
             if n:
-                L.dj_memcpy_d2h(out.ctypes.data, data, n * 8)
+                L.dj_memcpy_d2h(out.ctypes.data, data, out.nbytes)
             cols.append(out)
     L.dj_table_free(tbl_ptr)
     return cols
@@ -409,7 +485,9 @@ def hash_strings(offsets_ptr, chars_ptr, chars_bytes, n, seed=0):
 
 def cpp_shuffle_on_cols(comm, cols, n, on, hash_fn=HASH_MURMUR3, seed=0, compression=False):
     """shuffle_on over column descriptors (see cpp_distributed_inner_join_cols);
-    `on` lists the key column indices, STRING columns included."""
+    `on` lists the key column indices, STRING columns included. compression:
+    False/0 none, True/1 fixed bitpack policy, 2 sampling auto-select, 3 an
+    explicit cascaded option on every column (a loud error on float/bool)."""
     arr = (ColDesc * len(cols))()
     for i, c in enumerate(cols):
         arr[i].type_id = c[0]
@@ -419,8 +497,25 @@ def cpp_shuffle_on_cols(comm, cols, n, on, hash_fn=HASH_MURMUR3, seed=0, compres
     keys = np.asarray(on, dtype=np.int32)
     t = lib().dj_cpp_shuffle_on_cols(comm.ptr, ctypes.cast(arr, ctypes.c_void_p), len(cols), n,
                                      keys.ctypes.data, len(keys), hash_fn, seed,
-                                     int(bool(compression)))
+                                     int(compression))
     return table_to_numpy(t)
+
+
+def cpp_partition_cols(cols, n, on, nparts, hash_fn=HASH_MURMUR3, seed=0):
+    """The placement step of shuffle_on alone (test hook): returns
+    (numpy columns of the partitioned table, host offsets[nparts+1])."""
+    arr = (ColDesc * len(cols))()
+    for i, c in enumerate(cols):
+        arr[i].type_id = c[0]
+        arr[i].data = c[1]
+        arr[i].chars = c[2] if len(c) > 2 else None
+        arr[i].chars_bytes = c[3] if len(c) > 3 else 0
+    keys = np.asarray(on, dtype=np.int32)
+    offsets = np.zeros(nparts + 1, dtype=np.int64)
+    t = lib().dj_cpp_partition_cols(ctypes.cast(arr, ctypes.c_void_p), len(cols), n,
+                                    keys.ctypes.data, len(keys), nparts, hash_fn, seed,
+                                    offsets.ctypes.data)
+    return table_to_numpy(t), offsets
 
 
 def cpp_shuffle_on(comm, d_keys, d_pay, n, hash_fn=HASH_MURMUR3, seed=0,
@@ -431,6 +526,26 @@ def cpp_shuffle_on(comm, d_keys, d_pay, n, hash_fn=HASH_MURMUR3, seed=0,
     else:
         t = lib().dj_cpp_shuffle_on_i64(comm.ptr, d_keys.ptr, d_pay.ptr, n, hash_fn, seed)
     return table_to_numpy(t)
+
+
+GATHER_FUSED, GATHER_PER_COLUMN, GATHER_AUTO = 0, 1, 2
+
+
+class GatherDesc(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("width", ctypes.c_int)]
+
+
+def gather_columns(cols, d_idx_ptr, n, mode=GATHER_FUSED, reps=1):
+    """The table gather kernel through its test/bench hook: for each
+    (src_ptr, dst_ptr, width) in cols, dst[i] = src[idx[i]] for i < n.
+    Returns the per-repetition milliseconds."""
+    arr = (GatherDesc * max(len(cols), 1))()
+    for i, (src, dst, width) in enumerate(cols):
+        arr[i].src, arr[i].dst, arr[i].width = src, dst, width
+    ms = np.zeros(max(reps, 1), dtype=np.float64)
+    lib().dj_gather_columns(ctypes.cast(arr, ctypes.c_void_p), len(cols), d_idx_ptr, n, mode,
+                            reps, ms.ctypes.data)
+    return ms
 
 
 def timing(phase):

@@ -532,7 +532,10 @@ void dj_bucket_local_join(const int64_t* d_lk, const int64_t* d_lp, int64_t ln,
       dj_dfree(d_table);
     }
   }
-  neg1_fixup(retried);
+  /* the per-bucket fallback above is the only place a skew-flagged bucket's
+   * -1 rows are seen (join_build_pairs flags them): the snapshot taken
+   * before it is stale whenever it ran */
+  neg1_fixup(retried || any != 0);
 }
 
 int64_t dj_local_inner_join_global(const int64_t* d_lk, const int64_t* d_lp, int64_t ln,

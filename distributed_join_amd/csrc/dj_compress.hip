@@ -29,8 +29,10 @@
  *   num_RLEs ∈ {0,1}, num_deltas ∈ {0,1}, use_bp ∈ {0,1}; >1 passes raise
  *   at option validation (dj_cpp_api.hip). Without use_bp the subslices
  *   pack at width 64 (the raw fallback then usually wins on-device).
- * INT32 inputs are widened to i64 values before zigzag (they pack to their
- * natural width anyway). LZ4 is refused at validation: the wire targets
+ * 1-/2-/4-byte elements are sign-extended to i64 values before zigzag (they
+ * pack to their natural width anyway) and truncated back to the element
+ * width on the way out — lossless for unsigned columns too, since the same
+ * extension is undone by the truncation. LZ4 is refused at validation: the wire targets
  * xGMI, where cascaded already rarely pays.
  */
 #include "dj_error.hpp"
@@ -97,6 +99,35 @@ __device__ __forceinline__ int64_t load_elem(const void* p, int64_t i)
 {
   return (int64_t)((const T*)p)[i];
 }
+/* same, element size known only at run time */
+__device__ __forceinline__ int64_t load_elem_sized(const void* p, int elem_size, int64_t i)
+{
+  switch (elem_size) {
+    case 8: return load_elem<int64_t>(p, i);
+    case 4: return load_elem<int32_t>(p, i);
+    case 2: return load_elem<int16_t>(p, i);
+    default: return load_elem<int8_t>(p, i);
+  }
+}
+
+/* launch KERNEL<T> for the signed integer T of elem_size bytes */
+#define DJ_LAUNCH_BY_ELEM(KERNEL, elem_size, grid, s, ...)                               \
+  do {                                                                                   \
+    switch (elem_size) {                                                                 \
+      case 8:                                                                            \
+        hipLaunchKernelGGL((KERNEL<int64_t>), dim3(grid), dim3(CBLOCK), 0, s, __VA_ARGS__); \
+        break;                                                                           \
+      case 4:                                                                            \
+        hipLaunchKernelGGL((KERNEL<int32_t>), dim3(grid), dim3(CBLOCK), 0, s, __VA_ARGS__); \
+        break;                                                                           \
+      case 2:                                                                            \
+        hipLaunchKernelGGL((KERNEL<int16_t>), dim3(grid), dim3(CBLOCK), 0, s, __VA_ARGS__); \
+        break;                                                                           \
+      default:                                                                           \
+        hipLaunchKernelGGL((KERNEL<int8_t>), dim3(grid), dim3(CBLOCK), 0, s, __VA_ARGS__);  \
+        break;                                                                           \
+    }                                                                                    \
+  } while (0)
 
 __host__ __device__ inline size_t packed_bytes(int64_t n, uint32_t bits)
 {
@@ -188,10 +219,8 @@ __global__ void comp_pack_kernel(const void* __restrict__ in, int64_t count, int
     for (int j = 0; j < 32; j++) {
       int64_t i = g * 32 + j;
       if (i >= count) break;
-      int64_t v = elem_size == 8 ? ((const int64_t*)in)[i] : (int64_t)((const int32_t*)in)[i];
-      if (delta && i > 0)
-        v -= elem_size == 8 ? ((const int64_t*)in)[i - 1]
-                            : (int64_t)((const int32_t*)in)[i - 1];
+      int64_t v = load_elem_sized(in, elem_size, i);
+      if (delta && i > 0) v -= load_elem_sized(in, elem_size, i - 1);
       uint64_t z = zigzag(v);
       int64_t bitpos = (int64_t)j * bits;
       int word = (int)(bitpos >> 5);
@@ -518,17 +547,13 @@ void compress_slice_async(const void* d_in, int64_t count, int elem_size, int nu
                           int num_deltas, int use_bp, uint8_t* d_out, void* d_scratch,
                           hipStream_t s)
 {
-  DJ_CHECK_ERROR(elem_size == 4 || elem_size == 8, "cascaded: 4/8-byte elements only");
+  DJ_CHECK_ERROR(elem_size == 1 || elem_size == 2 || elem_size == 4 || elem_size == 8,
+                 "cascaded: 1/2/4/8-byte elements only");
   CompScratch scr = carve_comp_scratch(d_scratch, count);
   DJ_HIP_CALL(hipMemsetAsync(d_scratch, 0, 16, s));
   if (num_rles > 0 && count > 0) {
     const int64_t nchunks = (count + SCHUNK - 1) / SCHUNK;
-    if (elem_size == 8)
-      hipLaunchKernelGGL((rle_marks_kernel<int64_t>), dim3(cgrid(count)), dim3(CBLOCK), 0, s,
-                         d_in, count, scr.marks);
-    else
-      hipLaunchKernelGGL((rle_marks_kernel<int32_t>), dim3(cgrid(count)), dim3(CBLOCK), 0, s,
-                         d_in, count, scr.marks);
+    DJ_LAUNCH_BY_ELEM(rle_marks_kernel, elem_size, cgrid(count), s, d_in, count, scr.marks);
     DJ_HIP_CALL(hipGetLastError());
     hipLaunchKernelGGL(scan64_partials_kernel, dim3(cgrid(nchunks)), dim3(CBLOCK), 0, s,
                        scr.marks, count, nchunks, scr.partials);
@@ -536,14 +561,8 @@ void compress_slice_async(const void* d_in, int64_t count, int elem_size, int nu
     hipLaunchKernelGGL(scan64_exclusive_kernel, dim3(1), dim3(1024), 0, s, scr.partials,
                        nchunks);
     DJ_HIP_CALL(hipGetLastError());
-    if (elem_size == 8)
-      hipLaunchKernelGGL((rle_emit_kernel<int64_t>), dim3(cgrid(nchunks)), dim3(CBLOCK), 0, s,
-                         d_in, count, nchunks, scr.marks, scr.partials, scr.vals, scr.starts,
-                         scr.nruns);
-    else
-      hipLaunchKernelGGL((rle_emit_kernel<int32_t>), dim3(cgrid(nchunks)), dim3(CBLOCK), 0, s,
-                         d_in, count, nchunks, scr.marks, scr.partials, scr.vals, scr.starts,
-                         scr.nruns);
+    DJ_LAUNCH_BY_ELEM(rle_emit_kernel, elem_size, cgrid(nchunks), s, d_in, count, nchunks,
+                      scr.marks, scr.partials, scr.vals, scr.starts, scr.nruns);
     DJ_HIP_CALL(hipGetLastError());
     if (use_bp) {
       hipLaunchKernelGGL(rle_maxbits_kernel, dim3(cgrid(count)), dim3(CBLOCK), 0, s, scr.vals,
@@ -566,12 +585,8 @@ void compress_slice_async(const void* d_in, int64_t count, int elem_size, int nu
     return;
   }
   if (count > 0 && use_bp) {
-    if (elem_size == 8)
-      hipLaunchKernelGGL((comp_maxbits_kernel<int64_t>), dim3(cgrid(count)), dim3(CBLOCK), 0,
-                         s, d_in, count, num_deltas, scr.vbits);
-    else
-      hipLaunchKernelGGL((comp_maxbits_kernel<int32_t>), dim3(cgrid(count)), dim3(CBLOCK), 0,
-                         s, d_in, count, num_deltas, scr.vbits);
+    DJ_LAUNCH_BY_ELEM(comp_maxbits_kernel, elem_size, cgrid(count), s, d_in, count, num_deltas,
+                      scr.vbits);
     DJ_HIP_CALL(hipGetLastError());
   }
   hipLaunchKernelGGL(comp_header_kernel, dim3(1), dim3(64), 0, s, count, elem_size,
@@ -643,12 +658,7 @@ void decompress_slice_async(const uint8_t* d_comp, const CompSliceHeader& h, int
                          dim3(CBLOCK), 0, s, scr.vals, r, rchunks, scr.partials, scr.vals);
       DJ_HIP_CALL(hipGetLastError());
     }
-    if (elem_size == 8)
-      hipLaunchKernelGGL((rle_expand_kernel<int64_t>), dim3(cgrid(n)), dim3(CBLOCK), 0, s,
-                         scr.vals, scr.starts, r, n, d_out);
-    else
-      hipLaunchKernelGGL((rle_expand_kernel<int32_t>), dim3(cgrid(n)), dim3(CBLOCK), 0, s,
-                         scr.vals, scr.starts, r, n, d_out);
+    DJ_LAUNCH_BY_ELEM(rle_expand_kernel, elem_size, cgrid(n), s, scr.vals, scr.starts, r, n, d_out);
     DJ_HIP_CALL(hipGetLastError());
     return;
   }
@@ -665,20 +675,11 @@ void decompress_slice_async(const uint8_t* d_comp, const CompSliceHeader& h, int
     DJ_HIP_CALL(hipGetLastError());
     hipLaunchKernelGGL(scan64_exclusive_kernel, dim3(1), dim3(1024), 0, s, partials, nchunks);
     DJ_HIP_CALL(hipGetLastError());
-    if (elem_size == 8)
-      hipLaunchKernelGGL((scan64_finalize_kernel<int64_t>), dim3(cgrid(nchunks)),
-                         dim3(CBLOCK), 0, s, vals, n, nchunks, partials, d_out);
-    else
-      hipLaunchKernelGGL((scan64_finalize_kernel<int32_t>), dim3(cgrid(nchunks)),
-                         dim3(CBLOCK), 0, s, vals, n, nchunks, partials, d_out);
+    DJ_LAUNCH_BY_ELEM(scan64_finalize_kernel, elem_size, cgrid(nchunks), s, vals, n, nchunks,
+                      partials, d_out);
     DJ_HIP_CALL(hipGetLastError());
   } else {
-    if (elem_size == 8)
-      hipLaunchKernelGGL((comp_store_kernel<int64_t>), dim3(cgrid(n)), dim3(CBLOCK), 0, s,
-                         vals, n, d_out);
-    else
-      hipLaunchKernelGGL((comp_store_kernel<int32_t>), dim3(cgrid(n)), dim3(CBLOCK), 0, s,
-                         vals, n, d_out);
+    DJ_LAUNCH_BY_ELEM(comp_store_kernel, elem_size, cgrid(n), s, vals, n, d_out);
     DJ_HIP_CALL(hipGetLastError());
   }
 }

@@ -54,30 +54,32 @@ __global__ void iota_i64_kernel(int64_t* dst, int64_t n)
   for (; i < n; i += stride) dst[i] = i;
 }
 
-__global__ void gather_i64_kernel(const int64_t* __restrict__ src,
-                                  const int64_t* __restrict__ idx, int64_t n,
-                                  int64_t* __restrict__ dst)
-{
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) dst[i] = src[idx[i]];
-}
-
-__global__ void gather_i32_kernel(const int32_t* __restrict__ src,
-                                  const int64_t* __restrict__ idx, int64_t n,
-                                  int32_t* __restrict__ dst)
-{
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) dst[i] = src[idx[i]];
-}
-
-__global__ void widen_i32_kernel(const int32_t* __restrict__ src, int64_t n,
+/* narrow integer-rep key column -> the engine's int64 key (sign- or
+ * zero-extended per dj::load_key_i64) */
+__global__ void widen_key_kernel(const void* __restrict__ src, int kind, int64_t n,
                                  int64_t* __restrict__ dst)
 {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) dst[i] = src[i];
+  for (; i < n; i += stride) dst[i] = dj::load_key_i64(src, kind, i);
+}
+
+/* joined int64 key values back to a 1-/2-/4-byte key column (truncation
+ * inverts either extension) */
+__global__ void narrow_key_kernel(const int64_t* __restrict__ src, int64_t n, int width,
+                                  void* __restrict__ dst)
+{
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    const int64_t v = src[i];
+    if (width == 4)
+      ((int32_t*)dst)[i] = (int32_t)v;
+    else if (width == 2)
+      ((int16_t*)dst)[i] = (int16_t)v;
+    else
+      ((int8_t*)dst)[i] = (int8_t)v;
+  }
 }
 
 /* small owning device buffer (pool-backed: hipMallocAsync on the compute
@@ -184,7 +186,7 @@ void sync_streams()
  * h to 4 bits so tests can exercise that filter deterministically. */
 __global__ void fuse_keys_kernel(const int64_t* __restrict__ c0, const int64_t* __restrict__ c1,
                                  const int64_t* __restrict__ c2, const int64_t* __restrict__ c3,
-                                 uint32_t wide_mask /*bit c: col c is int64*/, int ncols,
+                                 uint32_t kinds /*4 bits per col: dj::kKey* */, int ncols,
                                  int64_t n, int weak, int64_t* __restrict__ out)
 {
   const int64_t* cols[4] = {c0, c1, c2, c3};
@@ -193,7 +195,7 @@ __global__ void fuse_keys_kernel(const int64_t* __restrict__ c0, const int64_t* 
   for (; i < n; i += stride) {
     uint64_t h = 0x9e3779b97f4a7c15ull;
     for (int c = 0; c < ncols; c++) {
-      int64_t v = (wide_mask >> c) & 1 ? cols[c][i] : (int64_t)((const int32_t*)cols[c])[i];
+      int64_t v = dj::load_key_i64(cols[c], (int)((kinds >> (4 * c)) & 0xF), i);
       h = dj_mix64(h ^ (uint64_t)v);
     }
     out[i] = weak ? (int64_t)(h & 0xF) : (int64_t)h;
@@ -201,6 +203,42 @@ __global__ void fuse_keys_kernel(const int64_t* __restrict__ c0, const int64_t* 
 }
 
 bool is_string(cudf::column_view col) { return col.type().id() == cudf::type_id::STRING; }
+
+/* dj::kKey* kind of an integer-rep key column; FLOAT32/FLOAT64 keys refuse
+ * loudly (cuDF normalises -0.0/NaN before hashing float keys; that is not
+ * implemented — INTEGRATION.md "Known restrictions") */
+int key_kind(cudf::data_type t)
+{
+  DJ_CHECK_ERROR(!cudf::is_floating(t),
+                 "FLOAT32/FLOAT64 columns cannot be join/shuffle keys (payload only)");
+  DJ_CHECK_ERROR(cudf::is_integer_rep(t),
+                 "join/shuffle key columns must be integer-rep or STRING columns");
+  const bool u = cudf::is_unsigned_rep(t);
+  switch (cudf::size_of(t)) {
+    case 8: return dj::kKeyI64;
+    case 4: return u ? dj::kKeyU32 : dj::kKeyI32;
+    case 2: return u ? dj::kKeyU16 : dj::kKeyI16;
+    default: return u ? dj::kKeyU8 : dj::kKeyI8;
+  }
+}
+
+bool is_new_type(cudf::data_type t) { return (int)t.id() >= (int)cudf::type_id::INT16; }
+
+/* a key pair may mix the long-standing reps (INT32 with INT64, chrono with
+ * its integer rep); a pair involving INT16, an unsigned type or BOOL8 must match exactly */
+void check_key_pairs(cudf::table_view left, cudf::table_view right,
+                     std::vector<cudf::size_type> const& lon,
+                     std::vector<cudf::size_type> const& ron)
+{
+  for (size_t c = 0; c < lon.size() && c < ron.size(); c++) {
+    const cudf::data_type lt = left.column(lon[c]).type(), rt = right.column(ron[c]).type();
+    if (lt.id() != cudf::type_id::STRING) (void)key_kind(lt);
+    if (rt.id() != cudf::type_id::STRING) (void)key_kind(rt);
+    DJ_CHECK_ERROR(lt == rt || (!is_new_type(lt) && !is_new_type(rt)),
+                   "join key pair: INT16/UINT8/UINT16/UINT32/UINT64/BOOL8 key columns must "
+                   "have the same type on both sides");
+  }
+}
 
 bool any_string_key(cudf::table_view t, std::vector<cudf::size_type> const& on)
 {
@@ -218,7 +256,7 @@ DBuf fuse_keys(cudf::table_view t, std::vector<cudf::size_type> const& on, hipSt
   DJ_CHECK_ERROR(on.size() >= 1 && on.size() <= 4,
                  "multi-column join keys: 1..4 key columns supported");
   const int64_t* ptrs[4] = {nullptr, nullptr, nullptr, nullptr};
-  uint32_t wide = 0;
+  uint32_t kinds = 0;
   std::vector<DBuf> str_keys;
   for (size_t c = 0; c < on.size(); c++) {
     cudf::column_view col = t.column(on[c]);
@@ -227,19 +265,17 @@ DBuf fuse_keys(cudf::table_view t, std::vector<cudf::size_type> const& on, hipSt
       dj::hash_strings(col.head<int32_t>(), (const uint8_t*)col.chars(), n,
                        (uint64_t*)str_keys.back().p, st);
       ptrs[c] = str_keys.back().i64();
-      wide |= 1u << c;
+      kinds |= (uint32_t)dj::kKeyI64 << (4 * c);
       continue;
     }
-    DJ_CHECK_ERROR(cudf::is_rep_int64(col.type()) || cudf::is_rep_int32(col.type()),
-                   "join/shuffle key columns must be integer-rep or STRING columns");
     ptrs[c] = col.head<int64_t>();
-    if (cudf::is_rep_int64(col.type())) wide |= 1u << c;
+    kinds |= (uint32_t)key_kind(col.type()) << (4 * c);
   }
   static const int weak = getenv("DJ_TEST_WEAK_FUSE") ? 1 : 0;
   DBuf out((size_t)(n > 0 ? n : 1) * 8);
   if (n > 0) {
     hipLaunchKernelGGL(fuse_keys_kernel, dim3(grid_for_n(n)), dim3(kBlock), 0, st, ptrs[0],
-                       ptrs[1], ptrs[2], ptrs[3], wide, (int)on.size(), n, weak, out.i64());
+                       ptrs[1], ptrs[2], ptrs[3], kinds, (int)on.size(), n, weak, out.i64());
     DJ_HIP_CALL(hipGetLastError());
     /* the row-hash temporaries go back to the pool on return */
     if (!str_keys.empty()) DJ_HIP_CALL(hipStreamSynchronize(st));
@@ -249,12 +285,11 @@ DBuf fuse_keys(cudf::table_view t, std::vector<cudf::size_type> const& on, hipSt
 
 const int64_t* key_as_i64(cudf::column_view col, DBuf& tmp)
 {
-  if (cudf::is_rep_int64(col.type())) return col.head<int64_t>();
-  DJ_CHECK_ERROR(cudf::is_rep_int32(col.type()),
-                 "join/shuffle key column must have a 4- or 8-byte integer rep");
+  const int kind = key_kind(col.type());
+  if (kind == dj::kKeyI64) return col.head<int64_t>();
   tmp = DBuf((size_t)col.size() * 8);
-  hipLaunchKernelGGL(widen_i32_kernel, dim3(grid_for_n(col.size())), dim3(kBlock), 0,
-                     dj_rt_stream(), col.head<int32_t>(), (int64_t)col.size(), tmp.i64());
+  hipLaunchKernelGGL(widen_key_kernel, dim3(grid_for_n(col.size())), dim3(kBlock), 0,
+                     dj_rt_stream(), col.head<void>(), kind, (int64_t)col.size(), tmp.i64());
   return tmp.i64();
 }
 
@@ -271,6 +306,19 @@ void validate_compression(std::vector<ColumnCompressionOptions> const& opts)
                                "dj_compress.hip wire format)");
     if (o.cascaded_format.num_deltas < 0 || o.cascaded_format.num_deltas > 1)
       throw std::runtime_error("cascaded num_deltas must be 0 or 1");
+  }
+}
+/* typed check: like the reference's cascaded dispatch (declared for the
+ * signed/unsigned integer types only), FLOAT32/FLOAT64/BOOL8 columns refuse
+ * a cascaded option instead of packing their bit patterns */
+void validate_compression(cudf::table_view t, std::vector<ColumnCompressionOptions> const& opts)
+{
+  validate_compression(opts);
+  for (cudf::size_type c = 0; c < t.num_columns() && (size_t)c < opts.size(); c++) {
+    const cudf::data_type ty = t.column(c).type();
+    if (opts[c].compression_method == CompressionMethod::cascaded &&
+        ty.id() != cudf::type_id::STRING && !cudf::is_cascaded_supported(ty))
+      throw std::runtime_error("Unsupported type for cascaded compressor");
   }
 }
 /* The GENERIC plan API (append_to_all_to_all_comm_buffers + all_to_all_comm
@@ -468,8 +516,13 @@ std::vector<ColumnCompressionOptions> generate_compression_options_distributed(
   bp.num_RLEs = 0;
   bp.num_deltas = 0;
   bp.use_bp = 1;
-  for (cudf::size_type c = 0; c < input.num_columns(); c++)
-    opts.emplace_back(CompressionMethod::cascaded, bp);
+  for (cudf::size_type c = 0; c < input.num_columns(); c++) {
+    const cudf::data_type ty = input.column(c).type();
+    if (ty.id() == cudf::type_id::STRING || cudf::is_cascaded_supported(ty))
+      opts.emplace_back(CompressionMethod::cascaded, bp);
+    else
+      opts.emplace_back(CompressionMethod::none);  // FLOAT32/FLOAT64/BOOL8
+  }
   return opts;
 }
 
@@ -506,9 +559,13 @@ nvcompCascadedFormatOpts select_cascaded_on_sample(const void* d_data, int64_t n
   if (esize == 8) {
     DJ_HIP_CALL(hipMemcpy(h.data(), d_data, (size_t)sample * 8, hipMemcpyDeviceToHost));
   } else {
-    std::vector<int32_t> h32((size_t)sample);
-    DJ_HIP_CALL(hipMemcpy(h32.data(), d_data, (size_t)sample * 4, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < sample; i++) h[(size_t)i] = h32[(size_t)i];
+    /* narrower elements enter as the codec loads them: sign-extended */
+    std::vector<int8_t> raw((size_t)sample * esize);
+    DJ_HIP_CALL(hipMemcpy(raw.data(), d_data, raw.size(), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < sample; i++)
+      h[(size_t)i] = esize == 4   ? (int64_t)((const int32_t*)raw.data())[i]
+                     : esize == 2 ? (int64_t)((const int16_t*)raw.data())[i]
+                                  : (int64_t)raw[(size_t)i];
   }
   auto zigzag = [](int64_t v) { return ((uint64_t)v << 1) ^ (uint64_t)(v >> 63); };
   auto packed_bits = [&](const std::vector<int64_t>& v, bool delta) {
@@ -574,11 +631,13 @@ std::vector<ColumnCompressionOptions> generate_auto_select_compression_options(
         select_cascaded_on_sample(col.child(0).head<int32_t>(), col.size() + 1, 4));
       kids.emplace_back(CompressionMethod::none);
       opts.emplace_back(CompressionMethod::none, nvcompCascadedFormatOpts{}, kids);
+    } else if (!cudf::is_cascaded_supported(col.type())) {
+      /* FLOAT32/FLOAT64/BOOL8: not cascaded-supported, as in the reference */
+      opts.emplace_back(CompressionMethod::none);
     } else {
       opts.emplace_back(
         CompressionMethod::cascaded,
-        select_cascaded_on_sample(col.head<char>(), col.size(),
-                                  cudf::is_rep_int64(col.type()) ? 8 : 4));
+        select_cascaded_on_sample(col.head<char>(), col.size(), cudf::size_of(col.type())));
     }
   }
   return opts;
@@ -749,7 +808,7 @@ void append_to_all_to_all_comm_buffers(cudf::table_view input,
   check_no_compression(compression_options);
   for (cudf::size_type c = 0; c < input.num_columns(); c++) {
     DJ_CHECK_ERROR(cudf::size_of(input.column(c).type()) > 0,
-                   "all-to-all: fixed-width (4/8-byte rep) columns only in this build");
+                   "all-to-all: fixed-width columns only through the generic plan API");
     std::vector<int64_t> soff(send_offsets.begin(), send_offsets.end());
     all_to_all_comm_buffers.emplace_back(
       input.column(c).head<int8_t>(), output.column(c).head<int8_t>(), soff, recv_offsets,
@@ -836,7 +895,7 @@ AllToAllCommunicator::AllToAllCommunicator(
     send_offsets(std::move(offsets)),
     compression_options(std::move(compression_options_))
 {
-  validate_compression(compression_options);
+  validate_compression(input_table, compression_options);
   DJ_CHECK_ERROR((int)send_offsets.size() == comm_group.size() + 1,
                  "AllToAllCommunicator: offsets must have comm_group.size()+1 entries");
   communicate_sizes(send_offsets, recv_offsets, comm_group, communicator);
@@ -999,7 +1058,7 @@ void AllToAllCommunicator::launch_communication(cudf::mutable_table_view communi
   auto add_buffer = [&](const void* src, void* dst, int esize,
                         const std::vector<int64_t>* so, const std::vector<int64_t>* ro,
                         const ColumnCompressionOptions& opt) {
-    if (opt.compression_method == CompressionMethod::cascaded && (esize == 4 || esize == 8)) {
+    if (opt.compression_method == CompressionMethod::cascaded) {
       Comp c;
       c.src = (const uint8_t*)src;
       c.dst = (uint8_t*)dst;
@@ -1078,7 +1137,10 @@ void AllToAllCommunicator::launch_communication(cudf::mutable_table_view communi
           dj::CompSliceHeader h;
           DJ_HIP_CALL(hipMemcpy(&h, (uint8_t*)c.comp.p + c.slot[i], sizeof(h),
                                 hipMemcpyDeviceToHost));
-          c.csize[i] = (int64_t)dj::compressed_size_from_header(h, c.esize);
+          /* wire slices are padded to 4 bytes (inside the slot's bound) so
+           * every received slice's packed words stay dword-aligned behind a
+           * raw 1-/2-byte slice of odd length */
+          c.csize[i] = ((int64_t)dj::compressed_size_from_header(h, c.esize) + 3) & ~(int64_t)3;
         }
         c.csend_off[i + 1] = c.csend_off[i] + c.csize[i];
       }
@@ -1219,6 +1281,53 @@ std::unique_ptr<cudf::column> gather_string_column(cudf::column_view src, const 
   return col;
 }
 
+/* output assembly: append to `cols` one n-row column per column of `src`,
+ * row i = src row idx[i]. All fixed-width columns go through ONE
+ * dj::gather_table call (the width-generic kernel, dj_kernels.hip "table
+ * gather"); STRING columns keep gather_string_column. The key column
+ * (key_col >= 0) is not gathered: its joined values already sit in key_vals
+ * as int64 (each random-line gather of 240 M rows costs ~5 ms; adopting the
+ * key buffer is free, narrowing to the key's own width is a streaming copy). */
+void gather_table_columns(cudf::table_view src, DBuf& idx, int64_t n, cudf::size_type key_col,
+                          DBuf* key_vals, std::vector<std::unique_ptr<cudf::column>>& cols,
+                          hipStream_t st)
+{
+  std::vector<dj::GatherCol> gc;
+  const int64_t* key_src = nullptr;
+  void* key_dst = nullptr;
+  int key_width = 0;
+  for (cudf::size_type c = 0; c < src.num_columns(); c++) {
+    cudf::column_view v = src.column(c);
+    if (v.type().id() == cudf::type_id::STRING) {
+      cols.push_back(gather_string_column(v, idx.i64(), n));
+      continue;
+    }
+    const int width = cudf::size_of(v.type());
+    DJ_CHECK_ERROR(width > 0, "gather: unsupported column type");
+    if (c == key_col && key_vals != nullptr) {
+      if (width == 8) {
+        cols.push_back(std::make_unique<cudf::column>(v.type(), (cudf::size_type)n, key_vals->p));
+        key_vals->p = nullptr;
+        continue;
+      }
+      auto col = std::make_unique<cudf::column>(v.type(), (cudf::size_type)n);
+      key_src = key_vals->i64();
+      key_dst = col->head();
+      key_width = width;
+      cols.push_back(std::move(col));
+      continue;
+    }
+    auto col = std::make_unique<cudf::column>(v.type(), (cudf::size_type)n);
+    gc.push_back(dj::GatherCol{v.head<void>(), col->head(), width});
+    cols.push_back(std::move(col));
+  }
+  dj_timing::Scope t(DJ_PHASE_GATHER, st);
+  if (key_dst != nullptr && n > 0)
+    hipLaunchKernelGGL(narrow_key_kernel, dim3(grid_for_n(n)), dim3(kBlock), 0, st, key_src, n,
+                       key_width, key_dst);
+  dj::gather_table(gc.data(), (int)gc.size(), idx.i64(), n, dj::kGatherAuto, st);
+}
+
 /* stable hash-partition of an arbitrary table into nparts contiguous ranges:
  * permutation computed on (key, iota) with the stable wave-ballot kernel,
  * then one gather per column. 2-column all-INT64 tables skip the gathers
@@ -1246,13 +1355,9 @@ PartitionedTable partition_table(cudf::table_view in, cudf::size_type key_col, i
                      in.column(1).type().id() == cudf::type_id::INT64;
 
   std::vector<std::unique_ptr<cudf::column>> cols;
-  for (cudf::size_type c = 0; c < in.num_columns(); c++) {
-    if (in.column(c).type().id() == cudf::type_id::STRING)
-      cols.push_back(std::make_unique<cudf::column>((cudf::size_type)0, (int64_t)0));
-    else
+  if (fast2)
+    for (cudf::size_type c = 0; c < 2; c++)
       cols.push_back(std::make_unique<cudf::column>(in.column(c).type(), (cudf::size_type)n));
-  }
-  auto out = std::make_unique<cudf::table>(std::move(cols));
 
   {
     dj_timing::Scope t1(DJ_PHASE_PART_COUNT, st);
@@ -1267,8 +1372,7 @@ PartitionedTable partition_table(cudf::table_view in, cudf::size_type key_col, i
     dj_timing::Scope t3(DJ_PHASE_PART_SCATTER, st);
     dj::partition_scatter(keys, in.column(pay_col).head<int64_t>(), n, nparts, hash_fn, seed,
                           d_off.i64(), scratch.p,
-                          (int64_t*)out->get_column(key_col).head(),
-                          (int64_t*)out->get_column(pay_col).head(), st);
+                          (int64_t*)cols[key_col]->head(), (int64_t*)cols[pay_col]->head(), st);
   } else {
     DBuf iota((size_t)n * 8), perm((size_t)n * 8), keys_out((size_t)n * 8);
     hipLaunchKernelGGL(iota_i64_kernel, dim3(grid_for_n(n)), dim3(kBlock), 0, st, iota.i64(), n);
@@ -1277,23 +1381,9 @@ PartitionedTable partition_table(cudf::table_view in, cudf::size_type key_col, i
       dj::partition_scatter(keys, iota.i64(), n, nparts, hash_fn, seed, d_off.i64(), scratch.p,
                             keys_out.i64(), perm.i64(), st);
     }
-    for (cudf::size_type c = 0; c < in.num_columns(); c++) {
-      if (cudf::is_rep_int64(in.column(c).type())) {
-        hipLaunchKernelGGL(gather_i64_kernel, dim3(grid_for_n(n)), dim3(kBlock), 0, st,
-                           in.column(c).head<int64_t>(), perm.i64(), n,
-                           (int64_t*)out->get_column(c).head());
-      } else if (cudf::is_rep_int32(in.column(c).type())) {
-        hipLaunchKernelGGL(gather_i32_kernel, dim3(grid_for_n(n)), dim3(kBlock), 0, st,
-                           in.column(c).head<int32_t>(), perm.i64(), n,
-                           (int32_t*)out->get_column(c).head());
-      } else if (in.column(c).type().id() == cudf::type_id::STRING) {
-        auto scol = gather_string_column(in.column(c), perm.i64(), n);
-        out->get_column(c) = std::move(*scol);
-      } else {
-        DJ_CHECK_ERROR(false, "partition: unsupported column type");
-      }
-    }
+    gather_table_columns(in, perm, n, -1, nullptr, cols, st);
   }
+  auto out = std::make_unique<cudf::table>(std::move(cols));
   std::vector<int64_t> off_host(nparts + 1);
   DJ_HIP_CALL(hipMemcpyAsync(off_host.data(), d_off.p, (size_t)(nparts + 1) * 8,
                              hipMemcpyDeviceToHost, st));
@@ -1306,14 +1396,6 @@ PartitionedTable partition_table(cudf::table_view in, cudf::size_type key_col, i
 
 /* local inner join of two tables via the bucketed-LDS engine; returns
  * left-cols + right-cols with keys duplicated, row order unspecified */
-__global__ void narrow_i64_to_i32_kernel(const int64_t* __restrict__ src, int64_t n,
-                                         int32_t* __restrict__ dst)
-{
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) dst[i] = (int32_t)src[i];
-}
-
 /* multi-key collision filter: keep (li, ri) pairs whose REAL key tuples are
  * equal (the bucket join matched on the fused hash; unequal tuples sharing a
  * fused value are hash collisions to drop). Output order is unspecified
@@ -1322,8 +1404,8 @@ __global__ void filter_tuple_matches_kernel(
   const int64_t* __restrict__ lc0, const int64_t* __restrict__ lc1,
   const int64_t* __restrict__ lc2, const int64_t* __restrict__ lc3,
   const int64_t* __restrict__ rc0, const int64_t* __restrict__ rc1,
-  const int64_t* __restrict__ rc2, const int64_t* __restrict__ rc3, uint32_t lwide,
-  uint32_t rwide, int nk, const int64_t* __restrict__ li, const int64_t* __restrict__ ri,
+  const int64_t* __restrict__ rc2, const int64_t* __restrict__ rc3, uint32_t lkinds,
+  uint32_t rkinds /*4 bits per col: dj::kKey* */, int nk, const int64_t* __restrict__ li, const int64_t* __restrict__ ri,
   int64_t n, int64_t* __restrict__ out_li, int64_t* __restrict__ out_ri,
   unsigned long long* __restrict__ count)
 {
@@ -1335,8 +1417,8 @@ __global__ void filter_tuple_matches_kernel(
     const int64_t a = li[i], b = ri[i];
     bool eq = true;
     for (int c = 0; c < nk; c++) {
-      int64_t lv = (lwide >> c) & 1 ? lc[c][a] : (int64_t)((const int32_t*)lc[c])[a];
-      int64_t rv = (rwide >> c) & 1 ? rc[c][b] : (int64_t)((const int32_t*)rc[c])[b];
+      int64_t lv = dj::load_key_i64(lc[c], (int)((lkinds >> (4 * c)) & 0xF), a);
+      int64_t rv = dj::load_key_i64(rc[c], (int)((rkinds >> (4 * c)) & 0xF), b);
       if (lv != rv) {
         eq = false;
         break;
@@ -1428,41 +1510,9 @@ std::unique_ptr<cudf::table> local_inner_join(cudf::table_view left, cudf::table
       o3.p = nullptr;
     } else {
       /* general: o1/o3 hold source row indices; gather every column —
-       * EXCEPT the key columns, whose joined values already sit in o0/o2
-       * (each random-line gather of 240 M rows costs ~5 ms; adopting the
-       * key buffer is free, narrowing to INT32 is a streaming copy) */
-      auto gather_col = [&](cudf::column_view src, DBuf& idx, DBuf* key_vals) {
-        if (key_vals != nullptr && src.type().id() != cudf::type_id::STRING) {
-          if (cudf::is_rep_int64(src.type())) {
-            auto col = std::make_unique<cudf::column>(src.type(), (cudf::size_type)nout,
-                                                      key_vals->p);
-            key_vals->p = nullptr;
-            return col;
-          }
-          auto col = std::make_unique<cudf::column>(src.type(), (cudf::size_type)nout);
-          if (nout > 0)
-            hipLaunchKernelGGL(narrow_i64_to_i32_kernel, dim3(grid_for_n(nout)),
-                               dim3(kBlock), 0, st, key_vals->i64(), nout,
-                               (int32_t*)col->head());
-          return col;
-        }
-        if (src.type().id() == cudf::type_id::STRING)
-          return gather_string_column(src, idx.i64(), nout);
-        auto col = std::make_unique<cudf::column>(src.type(), (cudf::size_type)nout);
-        if (nout > 0) {
-          if (cudf::is_rep_int64(src.type()))
-            hipLaunchKernelGGL(gather_i64_kernel, dim3(grid_for_n(nout)), dim3(kBlock), 0, st,
-                               src.head<int64_t>(), idx.i64(), nout, (int64_t*)col->head());
-          else
-            hipLaunchKernelGGL(gather_i32_kernel, dim3(grid_for_n(nout)), dim3(kBlock), 0, st,
-                               src.head<int32_t>(), idx.i64(), nout, (int32_t*)col->head());
-        }
-        return col;
-      };
-      for (cudf::size_type c = 0; c < ncl; c++)
-        cols.push_back(gather_col(left.column(c), o1, c == left_on ? &o0 : nullptr));
-      for (cudf::size_type c = 0; c < ncr; c++)
-        cols.push_back(gather_col(right.column(c), o3, c == right_on ? &o2 : nullptr));
+       * EXCEPT the key columns, whose joined values already sit in o0/o2 */
+      gather_table_columns(left, o1, nout, left_on, &o0, cols, st);
+      gather_table_columns(right, o3, nout, right_on, &o2, cols, st);
       DJ_HIP_CALL(hipStreamSynchronize(st));
     }
     return std::make_unique<cudf::table>(std::move(cols));
@@ -1534,12 +1584,14 @@ std::unique_ptr<cudf::table> local_inner_join_multi(cudf::table_view left,
     /* drop fused-hash collisions against the real key columns */
     const int64_t* lptr[4] = {nullptr, nullptr, nullptr, nullptr};
     const int64_t* rptr[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t lwide = 0, rwide = 0;
+    uint32_t lkinds = 0, rkinds = 0;
     for (size_t c = 0; c < lon.size(); c++) {
       lptr[c] = left.column(lon[c]).head<int64_t>();
       rptr[c] = right.column(ron[c]).head<int64_t>();
-      if (cudf::is_rep_int64(left.column(lon[c]).type())) lwide |= 1u << c;
-      if (cudf::is_rep_int64(right.column(ron[c]).type())) rwide |= 1u << c;
+      if (!str_keys) {
+        lkinds |= (uint32_t)key_kind(left.column(lon[c]).type()) << (4 * c);
+        rkinds |= (uint32_t)key_kind(right.column(ron[c]).type()) << (4 * c);
+      }
     }
     DBuf li2((size_t)std::max<int64_t>(nout, 1) * 8);
     DBuf ri2((size_t)std::max<int64_t>(nout, 1) * 8);
@@ -1551,8 +1603,7 @@ std::unique_ptr<cudf::table> local_inner_join_multi(cudf::table_view left,
         dj::TupleKeyCol d{};
         d.data = col.head<void>();
         d.chars = (const uint8_t*)col.chars();
-        d.kind = is_string(col) ? dj::kKeyStr
-                                : cudf::is_rep_int64(col.type()) ? dj::kKeyI64 : dj::kKeyI32;
+        d.kind = is_string(col) ? (int)dj::kKeyStr : key_kind(col.type());
         return d;
       };
       for (size_t c = 0; c < lon.size(); c++) {
@@ -1564,7 +1615,7 @@ std::unique_ptr<cudf::table> local_inner_join_multi(cudf::table_view left,
     } else if (nout > 0) {
       hipLaunchKernelGGL(filter_tuple_matches_kernel, dim3(grid_for_n(nout)), dim3(kBlock),
                          0, st, lptr[0], lptr[1], lptr[2], lptr[3], rptr[0], rptr[1],
-                         rptr[2], rptr[3], lwide, rwide, (int)lon.size(), o1.i64(), o3.i64(),
+                         rptr[2], rptr[3], lkinds, rkinds, (int)lon.size(), o1.i64(), o3.i64(),
                          nout, li2.i64(), ri2.i64(), (unsigned long long*)d_cnt.p);
       DJ_HIP_CALL(hipGetLastError());
     }
@@ -1574,21 +1625,8 @@ std::unique_ptr<cudf::table> local_inner_join_multi(cudf::table_view left,
     if (m == 0) return make_empty();
 
     std::vector<std::unique_ptr<cudf::column>> cols;
-    auto gather_col = [&](cudf::column_view src, DBuf& idx) {
-      if (src.type().id() == cudf::type_id::STRING)
-        return gather_string_column(src, idx.i64(), m);
-      auto col = std::make_unique<cudf::column>(src.type(), (cudf::size_type)m);
-      if (cudf::is_rep_int64(src.type()))
-        hipLaunchKernelGGL(gather_i64_kernel, dim3(grid_for_n(m)), dim3(kBlock), 0, st,
-                           src.head<int64_t>(), idx.i64(), m, (int64_t*)col->head());
-      else
-        hipLaunchKernelGGL(gather_i32_kernel, dim3(grid_for_n(m)), dim3(kBlock), 0, st,
-                           src.head<int32_t>(), idx.i64(), m, (int32_t*)col->head());
-      return col;
-    };
-    for (cudf::size_type c = 0; c < ncl; c++) cols.push_back(gather_col(left.column(c), li2));
-    for (cudf::size_type c = 0; c < ncr; c++)
-      cols.push_back(gather_col(right.column(c), ri2));
+    gather_table_columns(left, li2, m, -1, nullptr, cols, st);
+    gather_table_columns(right, ri2, m, -1, nullptr, cols, st);
     DJ_HIP_CALL(hipStreamSynchronize(st));
     return std::make_unique<cudf::table>(std::move(cols));
   }
@@ -1946,8 +1984,9 @@ std::unique_ptr<cudf::table> distributed_inner_join(
   DJ_CHECK_ERROR(left_on.size() == right_on.size() && !left_on.empty(),
                  "left_on/right_on must name the same number of key columns");
   DJ_CHECK_ERROR(left_on.size() <= 4, "up to 4 join key columns supported");
-  validate_compression(left_compression_options);
-  validate_compression(right_compression_options);
+  validate_compression(left, left_compression_options);
+  validate_compression(right, right_compression_options);
+  check_key_pairs(left, right, left_on, right_on);
   /* composite keys and any STRING key join on the fused key chain */
   const bool fused_keys = left_on.size() > 1 || any_string_key(left, left_on) ||
                           any_string_key(right, right_on);
@@ -2079,9 +2118,9 @@ std::unique_ptr<cudf::table> distributed_inner_join(
     bt.o3 = DBuf((size_t)bt.cap * 8);
     bt.meta = DBuf(16);
     if (!fast2) {
-      if (bt.ln && cudf::is_rep_int32(left.column(left_on[0]).type()))
+      if (bt.ln && cudf::size_of(left.column(left_on[0]).type()) < 8)
         bt.lkw = DBuf((size_t)bt.ln * 8);
-      if (bt.rn && cudf::is_rep_int32(right.column(right_on[0]).type()))
+      if (bt.rn && cudf::size_of(right.column(right_on[0]).type()) < 8)
         bt.rkw = DBuf((size_t)bt.rn * 8);
     }
   }
@@ -2119,9 +2158,10 @@ std::unique_ptr<cudf::table> distributed_inner_join(
       rp = (const int64_t*)bt.rrecv->get_column(1).head();
     } else {
       auto widen_or_use = [&](cudf::column_view col, DBuf& w) -> const int64_t* {
-        if (cudf::is_rep_int64(col.type())) return col.head<int64_t>();
-        hipLaunchKernelGGL(widen_i32_kernel, dim3(grid_for_n(col.size())), dim3(kBlock), 0, st,
-                           col.head<int32_t>(), (int64_t)col.size(), w.i64());
+        const int kind = key_kind(col.type());
+        if (kind == dj::kKeyI64) return col.head<int64_t>();
+        hipLaunchKernelGGL(widen_key_kernel, dim3(grid_for_n(col.size())), dim3(kBlock), 0, st,
+                           col.head<void>(), kind, (int64_t)col.size(), w.i64());
         return w.i64();
       };
       lk = widen_or_use(bt.lrecv->view().column(left_on[0]), bt.lkw);
@@ -2196,37 +2236,9 @@ std::unique_ptr<cudf::table> distributed_inner_join(
       cols.push_back(adopt(bt.o3));
     } else {
       /* key columns adopt/narrow o0/o2 (joined key values) instead of a
-       * random-line gather — see local_inner_join's assembly */
-      auto gather_col = [&](cudf::column_view src, DBuf& idx, DBuf* key_vals) {
-        if (key_vals != nullptr && src.type().id() != cudf::type_id::STRING) {
-          if (cudf::is_rep_int64(src.type())) {
-            auto col = std::make_unique<cudf::column>(src.type(), (cudf::size_type)nout,
-                                                      key_vals->p);
-            key_vals->p = nullptr;
-            return col;
-          }
-          auto col = std::make_unique<cudf::column>(src.type(), (cudf::size_type)nout);
-          hipLaunchKernelGGL(narrow_i64_to_i32_kernel, dim3(grid_for_n(nout)), dim3(kBlock),
-                             0, st, key_vals->i64(), nout, (int32_t*)col->head());
-          return col;
-        }
-        if (src.type().id() == cudf::type_id::STRING)
-          return gather_string_column(src, idx.i64(), nout);
-        auto col = std::make_unique<cudf::column>(src.type(), (cudf::size_type)nout);
-        if (cudf::is_rep_int64(src.type()))
-          hipLaunchKernelGGL(gather_i64_kernel, dim3(grid_for_n(nout)), dim3(kBlock), 0, st,
-                             src.head<int64_t>(), idx.i64(), nout, (int64_t*)col->head());
-        else
-          hipLaunchKernelGGL(gather_i32_kernel, dim3(grid_for_n(nout)), dim3(kBlock), 0, st,
-                             src.head<int32_t>(), idx.i64(), nout, (int32_t*)col->head());
-        return col;
-      };
-      for (cudf::size_type c = 0; c < left.num_columns(); c++)
-        cols.push_back(
-          gather_col(bt.lrecv->view().column(c), bt.o1, c == left_on[0] ? &bt.o0 : nullptr));
-      for (cudf::size_type c = 0; c < right.num_columns(); c++)
-        cols.push_back(
-          gather_col(bt.rrecv->view().column(c), bt.o3, c == right_on[0] ? &bt.o2 : nullptr));
+       * random-line gather — see gather_table_columns */
+      gather_table_columns(bt.lrecv->view(), bt.o1, nout, left_on[0], &bt.o0, cols, st);
+      gather_table_columns(bt.rrecv->view(), bt.o3, nout, right_on[0], &bt.o2, cols, st);
       DJ_HIP_CALL(hipStreamSynchronize(st));
     }
     batch_results.push_back(std::make_unique<cudf::table>(std::move(cols)));
@@ -2255,6 +2267,7 @@ std::unique_ptr<cudf::table> shuffle_on(cudf::table_view const& input,
   const int hash_fn =
     hash_function == cudf::hash_id::HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3;
   DJ_CHECK_ERROR(on_columns.size() <= 4, "shuffle_on: up to 4 key columns supported");
+  validate_compression(input, compression_options);
   /* multi-column keys, and any STRING key: placement on the fused key chain
    * (our spec, dj_hash.h — MurmurHash3 placement is parity-unpinned,
    * SURVEY.md §8c) */
@@ -2294,9 +2307,7 @@ std::unique_ptr<cudf::table> shuffle_on(cudf::table_view const& input,
 
 /* --------------------------------------------------------- distribute_table */
 
-namespace {
-constexpr int kMaxSchemaCols = 32;
-}
+using dj::kMaxSchemaCols;
 
 std::unique_ptr<cudf::table> distribute_table(cudf::table_view global_table,
                                               Communicator* communicator)
@@ -2700,7 +2711,12 @@ void* dj_cpp_distributed_inner_join_cols_multi(void* comm, const dj_col_desc* lc
 }
 
 /* shuffle_on over column descriptors; `on` names nkeys key columns, STRING
- * ones included (placement on the fused key chain, dj_hash.h) */
+ * ones included (placement on the fused key chain, dj_hash.h).
+ * compression: 0 = none, 1 = the fixed bitpack policy
+ * (generate_compression_options_distributed), 2 = sampling auto-select
+ * (generate_auto_select_compression_options), 3 = an explicit bitpack
+ * cascaded option on EVERY column, whatever its type (reaches the option
+ * validation: a loud error on FLOAT32/FLOAT64/BOOL8 columns). */
 void* dj_cpp_shuffle_on_cols(void* comm, const dj_col_desc* cols, int nc, int64_t n,
                              const int32_t* on, int nkeys, int hash_function, uint32_t seed,
                              int compression)
@@ -2718,13 +2734,89 @@ void* dj_cpp_shuffle_on_cols(void* comm, const dj_col_desc* cols, int nc, int64_
   }
   cudf::table_view input(v);
   std::vector<cudf::size_type> keys(on, on + nkeys);
-  auto opts = generate_compression_options_distributed(input, compression != 0);
-  auto result =
-    shuffle_on(input, keys, (Communicator*)comm, opts,
-               hash_function == DJ_HASH_IDENTITY ? cudf::hash_id::HASH_IDENTITY
-                                                 : cudf::hash_id::HASH_MURMUR3,
-               seed, false, nullptr);
-  return result.release();
+  std::vector<ColumnCompressionOptions> opts;
+  if (compression == 2) {
+    opts = generate_auto_select_compression_options(input);
+  } else if (compression == 3) {
+    nvcompCascadedFormatOpts bp{};
+    bp.use_bp = 1;
+    opts.assign((size_t)nc, ColumnCompressionOptions(CompressionMethod::cascaded, bp));
+  } else {
+    opts = generate_compression_options_distributed(input, compression != 0);
+  }
+  try {
+    auto result =
+      shuffle_on(input, keys, (Communicator*)comm, opts,
+                 hash_function == DJ_HASH_IDENTITY ? cudf::hash_id::HASH_IDENTITY
+                                                   : cudf::hash_id::HASH_MURMUR3,
+                 seed, false, nullptr);
+    return result.release();
+  } catch (std::exception const& e) {
+    /* no exception crosses the C ABI: loud exit, as DJ_CHECK_ERROR */
+    fprintf(stderr, "ERROR: %s\n", e.what());
+    exit(1);
+  }
+}
+
+/* test hook: the placement step of shuffle_on alone. Partitions the table
+ * into nparts contiguous ranges exactly as shuffle_on does before its
+ * all-to-all (same key widening / fused chain, same stable partition, same
+ * table gather) and writes the nparts+1 row offsets to h_offsets. Lets one
+ * GPU check placement against the dj_hash.h spec for nparts > 1. */
+void* dj_cpp_partition_cols(const dj_col_desc* cols, int nc, int64_t n, const int32_t* on,
+                            int nkeys, int nparts, int hash_function, uint32_t seed,
+                            int64_t* h_offsets)
+{
+  using cudf::column_view;
+  using cudf::data_type;
+  using cudf::type_id;
+  std::vector<column_view> v;
+  for (int c = 0; c < nc; c++) {
+    if ((type_id)cols[c].type_id == type_id::STRING)
+      v.emplace_back(data_type(type_id::STRING), (cudf::size_type)n, cols[c].data,
+                     cols[c].chars, cols[c].chars_bytes);
+    else
+      v.emplace_back(data_type((type_id)cols[c].type_id), (cudf::size_type)n, cols[c].data);
+  }
+  cudf::table_view input(v);
+  std::vector<cudf::size_type> keys(on, on + nkeys);
+  DJ_CHECK_ERROR(nkeys >= 1 && nkeys <= 4, "partition: 1..4 key columns");
+  DJ_CHECK_ERROR(nparts >= 1 && nparts <= dj::kMaxPartitions, "partition: 1..1024 parts");
+  const int hash_fn = hash_function == DJ_HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3;
+  DBuf fused;
+  if (nkeys > 1 || any_string_key(input, keys)) {
+    DJ_CHECK_ERROR(hash_fn != DJ_HASH_IDENTITY,
+                   "identity-hash placement requires a single integer key column");
+    fused = fuse_keys(input, keys, dj_rt_stream());
+  }
+  PartitionedTable part =
+    partition_table(input, keys[0], nparts, hash_fn, seed, fused.p ? fused.i64() : nullptr);
+  for (int i = 0; i <= nparts; i++) h_offsets[i] = part.offsets[(size_t)i];
+  return part.tbl.release();
+}
+
+/* test/bench hook for the table gather (include/distributed_join.h) */
+void dj_gather_columns(const dj_gather_desc* descs, int ncols, const int64_t* d_idx, int64_t n,
+                       int mode, int reps, double* h_ms)
+{
+  hipStream_t st = dj_rt_stream();
+  std::vector<dj::GatherCol> gc;
+  for (int c = 0; c < ncols; c++)
+    gc.push_back(dj::GatherCol{descs[c].src, descs[c].dst, descs[c].width});
+  hipEvent_t e0, e1;
+  DJ_HIP_CALL(hipEventCreate(&e0));
+  DJ_HIP_CALL(hipEventCreate(&e1));
+  for (int r = 0; r < (reps > 0 ? reps : 1); r++) {
+    DJ_HIP_CALL(hipEventRecord(e0, st));
+    dj::gather_table(gc.data(), ncols, d_idx, n, mode, st);
+    DJ_HIP_CALL(hipEventRecord(e1, st));
+    DJ_HIP_CALL(hipEventSynchronize(e1));
+    float ms = 0.f;
+    DJ_HIP_CALL(hipEventElapsedTime(&ms, e0, e1));
+    if (h_ms) h_ms[r] = ms;
+  }
+  DJ_HIP_CALL(hipEventDestroy(e0));
+  DJ_HIP_CALL(hipEventDestroy(e1));
 }
 
 /* test hook: d_out[i] = dj_murmur3_bytes(row i, seed) through the STRING-key

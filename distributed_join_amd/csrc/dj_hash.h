@@ -23,8 +23,10 @@
  *
  *   h = 0x9e3779b97f4a7c15;  for each key column c:  h = dj_mix64(h ^ v_c)
  *
- * where v_c is the integer value of an INT32/INT64-rep column (sign-extended)
- * and dj_string_key64(row bytes) of a STRING column (dj_strhash.h: two
+ * where v_c is the integer value of an integer-rep column as int64 (signed
+ * reps sign-extended, UINT8/UINT16/UINT32/BOOL8 zero-extended, UINT64
+ * reinterpreted — the same widening a single narrow key gets before
+ * dj_row_hash) and dj_string_key64(row bytes) of a STRING column (dj_strhash.h: two
  * MurmurHash3_x86_32 halves, seeds 0 and 0x9747B28C). Placement is then
  * dj_murmur3_int64(fused, seed) % nparts, exactly as for an int64 key. A
  * single STRING key takes the same chain. The join matches on the fused

@@ -24,6 +24,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 namespace dj {
 
 constexpr int BLOCK = 256;
@@ -136,6 +138,9 @@ void neg1_cross_join(const int64_t* d_lk, const int64_t* d_lp, int64_t ln,
     int64_t base = 0;
     DJ_HIP_CALL(hipMemcpyAsync(&base, d_counter, 8, hipMemcpyDeviceToHost, s));
     DJ_HIP_CALL(hipStreamSynchronize(s));
+    /* narrow signed keys make -1 a frequent value on both sides */
+    DJ_CHECK_ERROR(n1 <= INT64_MAX / n2,
+                   "join: cross product of the -1 keys overflows int64 rows");
     const int64_t total = n1 * n2;
     hipLaunchKernelGGL(emit_neg1_cross_kernel, dim3(grid_for(total)), dim3(BLOCK), 0, s,
                        d_lpv, n1, d_rpv, n2, base, d_out0, d_out1, d_out2, d_out3, cap);
@@ -154,6 +159,177 @@ void fill_i64(int64_t* d_dst, int64_t value, int64_t n, hipStream_t s)
   if (n <= 0) return;
   hipLaunchKernelGGL(fill_i64_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, s, d_dst, value, n);
   DJ_HIP_CALL(hipGetLastError());
+}
+
+/* ----------------------------------------------------------- table gather
+ *
+ * Output assembly of the general (non-fast2) join and of partition_table:
+ * every fixed-width column of a table is gathered through the same row-index
+ * array. The per-column form (one launch per column, one row per thread)
+ * re-reads the 8-byte index for every column and stores 1-/2-byte elements
+ * one at a time. The fused form takes all columns of the table in one launch
+ * through a by-value descriptor: a thread owns four consecutive output rows,
+ * loads its four indices once (two 16 B loads), and for each column loads the
+ * four indexed elements and writes them as one packed store — a dword for
+ * 1-byte, 8 B for 2-byte, 16 B for 4-byte and 2 x 16 B for 8-byte columns.
+ * The last n % 4 rows go through a scalar tail. Sources are only
+ * element-aligned (a partition slice starts at any row); destinations are
+ * 16-byte aligned (checked by the launcher), so row 4q of any width sits on
+ * its packed store's natural boundary. Which widths the engine routes to
+ * which form is decided by measurement: kFusedWidths below, DESIGN.md. */
+
+template <typename T>
+__global__ void gather_col_kernel(const T* __restrict__ src, const int64_t* __restrict__ idx,
+                                  int64_t n, T* __restrict__ dst)
+{
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) dst[i] = src[idx[i]];
+}
+
+__global__ __launch_bounds__(BLOCK) void gather_table_kernel(GatherDesc d,
+                                                             const int64_t* __restrict__ idx,
+                                                             int64_t n, int idx_aligned16)
+{
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nquads = n >> 2;
+  for (int64_t q = tid; q < nquads; q += stride) {
+    int64_t i0, i1, i2, i3;
+    if (idx_aligned16) {
+      const longlong2 a = nt_load2((const longlong2*)idx + 2 * q);
+      const longlong2 b = nt_load2((const longlong2*)idx + 2 * q + 1);
+      i0 = a.x, i1 = a.y, i2 = b.x, i3 = b.y;
+    } else {
+      i0 = nt_load(idx + 4 * q);
+      i1 = nt_load(idx + 4 * q + 1);
+      i2 = nt_load(idx + 4 * q + 2);
+      i3 = nt_load(idx + 4 * q + 3);
+    }
+    for (int c = 0; c < d.ncols; c++) {
+      const GatherCol col = d.col[c];
+      switch (col.width) {
+        case 1: {
+          const uint8_t* s = (const uint8_t*)col.src;
+          const uint32_t v = (uint32_t)s[i0] | ((uint32_t)s[i1] << 8) |
+                             ((uint32_t)s[i2] << 16) | ((uint32_t)s[i3] << 24);
+          ((uint32_t*)col.dst)[q] = v;
+          break;
+        }
+        case 2: {
+          const uint16_t* s = (const uint16_t*)col.src;
+          uint2 v;
+          v.x = (uint32_t)s[i0] | ((uint32_t)s[i1] << 16);
+          v.y = (uint32_t)s[i2] | ((uint32_t)s[i3] << 16);
+          ((uint2*)col.dst)[q] = v;
+          break;
+        }
+        case 4: {
+          const uint32_t* s = (const uint32_t*)col.src;
+          uint4 v;
+          v.x = s[i0];
+          v.y = s[i1];
+          v.z = s[i2];
+          v.w = s[i3];
+          ((uint4*)col.dst)[q] = v;
+          break;
+        }
+        default: {
+          const uint64_t* s = (const uint64_t*)col.src;
+          ulonglong2 a, b;
+          a.x = s[i0];
+          a.y = s[i1];
+          b.x = s[i2];
+          b.y = s[i3];
+          ((ulonglong2*)col.dst)[2 * q] = a;
+          ((ulonglong2*)col.dst)[2 * q + 1] = b;
+          break;
+        }
+      }
+    }
+  }
+  /* scalar tail: rows [4*nquads, n), one per thread of the first block */
+  const int64_t t = (nquads << 2) + tid;
+  if (t < n) {
+    const int64_t i = idx[t];
+    for (int c = 0; c < d.ncols; c++) {
+      const GatherCol col = d.col[c];
+      switch (col.width) {
+        case 1: ((uint8_t*)col.dst)[t] = ((const uint8_t*)col.src)[i]; break;
+        case 2: ((uint16_t*)col.dst)[t] = ((const uint16_t*)col.src)[i]; break;
+        case 4: ((uint32_t*)col.dst)[t] = ((const uint32_t*)col.src)[i]; break;
+        default: ((uint64_t*)col.dst)[t] = ((const uint64_t*)col.src)[i]; break;
+      }
+    }
+  }
+}
+
+/* widths (bit w set: w-byte columns) that kGatherAuto sends through the fused
+ * kernel; the rest take one per-column launch each. Measured on MI355X
+ * (DESIGN.md "Table gather", profiles/wide_table_bench_mi355x.json): the
+ * gather is bound by the random source lines, not by index traffic, and a
+ * 1- or 2-byte source column alone stays cache-resident while four of them
+ * interleaved do not — fused is 17% (1-byte) and 6% (2-byte) slower there,
+ * level at 4 bytes and ahead at 8. */
+constexpr unsigned kFusedWidths = (1u << 4) | (1u << 8);
+
+static void launch_gather_fused(const GatherDesc& d, const int64_t* d_idx, int64_t n,
+                                hipStream_t s)
+{
+  const int64_t nthreads = std::max<int64_t>(n >> 2, 4);
+  hipLaunchKernelGGL(gather_table_kernel, dim3(grid_for(nthreads)), dim3(BLOCK), 0, s, d,
+                     d_idx, n, ((uintptr_t)d_idx & 15) == 0 ? 1 : 0);
+  DJ_HIP_CALL(hipGetLastError());
+}
+
+void gather_table(const GatherCol* cols, int ncols, const int64_t* d_idx, int64_t n, int mode,
+                  hipStream_t s)
+{
+  DJ_CHECK_ERROR(mode == kGatherFused || mode == kGatherPerColumn || mode == kGatherAuto,
+                 "gather_table: unknown mode");
+  for (int c = 0; c < ncols; c++) {
+    const int w = cols[c].width;
+    DJ_CHECK_ERROR(w == 1 || w == 2 || w == 4 || w == 8,
+                   "gather_table: column width must be 1, 2, 4 or 8 bytes");
+  }
+  if (n <= 0 || ncols <= 0) return;
+  GatherDesc d;
+  d.ncols = 0;
+  for (int c = 0; c < ncols; c++) {
+    const GatherCol& col = cols[c];
+    const bool fused =
+      mode == kGatherFused || (mode == kGatherAuto && ((kFusedWidths >> col.width) & 1u));
+    if (fused) {
+      DJ_CHECK_ERROR(((uintptr_t)col.dst & 15) == 0,
+                     "gather_table: fused destinations must be 16-byte aligned");
+      d.col[d.ncols++] = col;
+      if (d.ncols == kMaxSchemaCols) {
+        launch_gather_fused(d, d_idx, n, s);
+        d.ncols = 0;
+      }
+      continue;
+    }
+    switch (col.width) {
+      case 1:
+        hipLaunchKernelGGL((gather_col_kernel<uint8_t>), dim3(grid_for(n)), dim3(BLOCK), 0, s,
+                           (const uint8_t*)col.src, d_idx, n, (uint8_t*)col.dst);
+        break;
+      case 2:
+        hipLaunchKernelGGL((gather_col_kernel<uint16_t>), dim3(grid_for(n)), dim3(BLOCK), 0, s,
+                           (const uint16_t*)col.src, d_idx, n, (uint16_t*)col.dst);
+        break;
+      case 4:
+        hipLaunchKernelGGL((gather_col_kernel<uint32_t>), dim3(grid_for(n)), dim3(BLOCK), 0, s,
+                           (const uint32_t*)col.src, d_idx, n, (uint32_t*)col.dst);
+        break;
+      default:
+        hipLaunchKernelGGL((gather_col_kernel<uint64_t>), dim3(grid_for(n)), dim3(BLOCK), 0, s,
+                           (const uint64_t*)col.src, d_idx, n, (uint64_t*)col.dst);
+        break;
+    }
+    DJ_HIP_CALL(hipGetLastError());
+  }
+  if (d.ncols > 0) launch_gather_fused(d, d_idx, n, s);
 }
 
 /* ------------------------------------------------------------- generator */

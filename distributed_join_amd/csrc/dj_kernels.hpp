@@ -201,7 +201,30 @@ void hash_strings_seeded(const int32_t* d_offsets, const uint8_t* d_chars, int64
  * bytes); appends to d_out_li/d_out_ri at positions drawn from *d_count
  * (caller-zeroed), order unspecified. Per column and side: kind, data
  * (values, or int32 offsets for kKeyStr) and chars (kKeyStr only). */
-enum { kKeyI32 = 0, kKeyI64 = 1, kKeyStr = 2 };
+enum {
+  kKeyI32 = 0,
+  kKeyI64 = 1, /* also UINT64, reinterpreted */
+  kKeyStr = 2,
+  kKeyI8 = 3,
+  kKeyI16 = 4,
+  kKeyU8 = 5, /* also BOOL8 */
+  kKeyU16 = 6,
+  kKeyU32 = 7
+};
+/* element i of an integer-rep key column as the engine's int64 key: signed
+ * reps sign-extend, unsigned reps zero-extend */
+__host__ __device__ __forceinline__ int64_t load_key_i64(const void* p, int kind, int64_t i)
+{
+  switch (kind) {
+    case kKeyI64: return ((const int64_t*)p)[i];
+    case kKeyI32: return (int64_t)((const int32_t*)p)[i];
+    case kKeyU32: return (int64_t)((const uint32_t*)p)[i];
+    case kKeyI16: return (int64_t)((const int16_t*)p)[i];
+    case kKeyU16: return (int64_t)((const uint16_t*)p)[i];
+    case kKeyI8: return (int64_t)((const int8_t*)p)[i];
+    default: return (int64_t)((const uint8_t*)p)[i];
+  }
+}
 struct TupleKeyCol {
   const void* data;
   const uint8_t* chars;
@@ -252,6 +275,30 @@ void compress_slice_async(const void* d_in, int64_t count, int elem_size, int nu
 size_t compressed_size_from_header(const CompSliceHeader& h, int elem_size);
 void decompress_slice_async(const uint8_t* d_comp, const CompSliceHeader& h, int elem_size,
                             void* d_out, void* d_scratch, hipStream_t s);
+
+/* ----- table gather (dj_kernels.hip "table gather" block) -----
+ * dst[i] = src[idx[i]], i in [0, n), for every fixed-width column of a table
+ * through ONE index array. width is the element size in bytes (1/2/4/8);
+ * src may be any element-aligned address, dst must be 16-byte aligned (a
+ * fresh column from the arena is). Reads idx[0..n) and the indexed source
+ * elements, writes dst bytes [0, n*width) and nothing else. */
+constexpr int kMaxSchemaCols = 32;
+struct GatherCol {
+  const void* src;
+  void* dst;
+  int width;
+};
+struct GatherDesc {
+  GatherCol col[kMaxSchemaCols];
+  int ncols;
+};
+enum {
+  kGatherFused = 0,     /* one launch for all columns, 4 rows/thread, packed stores */
+  kGatherPerColumn = 1, /* one launch per column, 1 row/thread */
+  kGatherAuto = 2       /* per-width routing by measurement */
+};
+void gather_table(const GatherCol* cols, int ncols, const int64_t* d_idx, int64_t n, int mode,
+                  hipStream_t s);
 
 /* ----- small utilities ----- */
 void fill_i64(int64_t* d_dst, int64_t value, int64_t n, hipStream_t s);

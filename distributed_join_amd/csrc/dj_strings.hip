@@ -565,11 +565,7 @@ __global__ void filter_tuple_matches_mixed_kernel(TupleKeys keys, const int64_t*
         const int32_t l0 = lo[a], r0 = ro[b];
         eq = string_equal(lc.chars + l0, lo[a + 1] - l0, rc.chars + r0, ro[b + 1] - r0);
       } else {
-        const int64_t lv = lc.kind == kKeyI64 ? ((const int64_t*)lc.data)[a]
-                                              : (int64_t)((const int32_t*)lc.data)[a];
-        const int64_t rv = rc.kind == kKeyI64 ? ((const int64_t*)rc.data)[b]
-                                              : (int64_t)((const int32_t*)rc.data)[b];
-        eq = lv == rv;
+        eq = load_key_i64(lc.data, lc.kind, a) == load_key_i64(rc.data, rc.kind, b);
       }
     }
     if (eq) {

@@ -118,7 +118,8 @@ enum dj_phase {
   DJ_PHASE_BUCKET_SCAN = 10,
   DJ_PHASE_BUCKET_SCATTER = 11,
   DJ_PHASE_JOIN_FUSED = 12,
-  DJ_PHASE_COUNT_ = 13
+  DJ_PHASE_GATHER = 13, /* output assembly: the table gather + key narrowing */
+  DJ_PHASE_COUNT_ = 14
 };
 void dj_timing_enable(int on);
 void dj_timing_reset(void);
@@ -156,14 +157,20 @@ void dj_exchange_sizes(const int64_t* h_send_counts, int64_t* h_recv_counts);
 int dj_rccl_selftest(int64_t n);
 
 /* cascaded codec roundtrip (test hook): compress count elements of
- * elem_size (4/8) from d_in with {num_rles, num_deltas, use_bp} cascaded
+ * elem_size (1/2/4/8) from d_in with {num_rles, num_deltas, use_bp} cascaded
  * passes, decompress into d_out, return the wire size in bytes */
 int64_t dj_compress_roundtrip(const void* d_in, int64_t count, int elem_size, int num_rles,
                               int num_deltas, int use_bp, void* d_out);
 
 /* ---------------- column descriptors + STRING key columns.
- * A column handed over the C ABI: type_id is a cudf::type_id value (2=INT32,
- * 3=INT64, 4=STRING, ...); data is the fixed-width device array, or the
+ * A column handed over the C ABI: type_id is a cudf::type_id value
+ * (include/dj_cudf_types.hpp): 1=INT8, 2=INT32, 3=INT64, 4=STRING,
+ * 5..9=TIMESTAMP_{DAYS,SECONDS,MILLISECONDS,MICROSECONDS,NANOSECONDS},
+ * 10..14=DURATION_{same units}, 15=INT16, 16=UINT8, 17=UINT16, 18=UINT32,
+ * 19=UINT64, 20=FLOAT32, 21=FLOAT64, 22=BOOL8. Every fixed-width type is a
+ * valid payload column; all but FLOAT32/FLOAT64 are valid key columns (a key
+ * pair involving one of 15..22 must have identical type ids on both sides).
+ * data is the fixed-width device array (element-aligned), or the
  * int32 offsets[n+1] of a STRING column whose bytes are chars[0..chars_bytes).
  * The descriptor joins/shuffles take key indices that may name STRING
  * columns, alone or among up to 4 key columns (reference: arbitrary
@@ -195,6 +202,30 @@ void dj_hash_strings(const void* d_offsets, const void* d_chars, int64_t chars_b
  * Synchronizes. */
 void dj_string_keys64(const void* d_offsets, const void* d_chars, int64_t chars_bytes,
                       int64_t n, uint64_t* d_out, int reps, double* h_ms);
+
+
+/* test hook: the placement step of shuffle_on alone — partitions the table
+ * into nparts contiguous ranges exactly as shuffle_on does before its
+ * all-to-all and writes the nparts+1 row offsets to h_offsets (host). Returns
+ * the partitioned table. */
+void* dj_cpp_partition_cols(const dj_col_desc* cols, int nc, int64_t n, const int32_t* on,
+                            int nkeys, int nparts, int hash_function, uint32_t seed,
+                            int64_t* h_offsets);
+
+/* test/bench hook for the table gather kernel: for each of ncols descriptors
+ * dst[i] = src[idx[i]] for i in [0, n), elements of `width` bytes (1/2/4/8).
+ * mode 0 = the fused width-generic kernel (all columns in one launch, four
+ * rows per thread, packed stores; dst must be 16-byte aligned), mode 1 = one
+ * one-row-per-thread launch per column, mode 2 = the per-width routing the
+ * engine uses. Runs `reps` times, each between a hipEvent pair; h_ms (host
+ * double[reps], may be NULL) receives the milliseconds. Synchronizes. */
+typedef struct {
+  const void* src;
+  void* dst;
+  int width;
+} dj_gather_desc;
+void dj_gather_columns(const dj_gather_desc* descs, int ncols, const int64_t* d_idx, int64_t n,
+                       int mode, int reps, double* h_ms);
 
 #ifdef __cplusplus
 }

@@ -11,8 +11,11 @@
  * reference's interface touches is provided; column data lives in HIP device
  * memory (MI355X HBM3E). Do not link this together with real libcudf.
  *
- * v1 supports fixed-width INT32/INT64 columns (the BASELINE configs 1-3
- * types); STRING is declared for the config-4 path.
+ * Column types: every fixed-width type of 1, 2, 4 or 8 bytes declared in
+ * type_id below moves through partition, join, shuffle and the all-to-all
+ * as payload. Integer-rep types (signed, unsigned, BOOL8, chrono) and STRING
+ * are also valid join/shuffle keys; FLOAT32/FLOAT64 are payload-only (see
+ * INTEGRATION.md "Known restrictions").
  */
 #pragma once
 
@@ -44,6 +47,16 @@ enum class type_id : int32_t {
   DURATION_MILLISECONDS,
   DURATION_MICROSECONDS,
   DURATION_NANOSECONDS,
+  /* appended after the chrono block: values 0..14 above are C-ABI values
+   * (dj_col_desc.type_id) and never move */
+  INT16,
+  UINT8,
+  UINT16,
+  UINT32,
+  UINT64,
+  FLOAT32,
+  FLOAT64,
+  BOOL8,
 };
 
 struct data_type {
@@ -60,11 +73,19 @@ struct data_type {
 inline constexpr size_type size_of(data_type t)
 {
   switch (t.id()) {
-    case type_id::INT8: return 1;
+    case type_id::INT8:
+    case type_id::UINT8:
+    case type_id::BOOL8: return 1;
+    case type_id::INT16:
+    case type_id::UINT16: return 2;
     case type_id::INT32:
+    case type_id::UINT32:
+    case type_id::FLOAT32:
     case type_id::TIMESTAMP_DAYS:
     case type_id::DURATION_DAYS: return 4;
     case type_id::INT64:
+    case type_id::UINT64:
+    case type_id::FLOAT64:
     case type_id::TIMESTAMP_SECONDS:
     case type_id::TIMESTAMP_MILLISECONDS:
     case type_id::TIMESTAMP_MICROSECONDS:
@@ -80,6 +101,29 @@ inline constexpr size_type size_of(data_type t)
 /* fixed-width 4-/8-byte classification used by the join/partition engine */
 inline constexpr bool is_rep_int32(data_type t) { return size_of(t) == 4; }
 inline constexpr bool is_rep_int64(data_type t) { return size_of(t) == 8; }
+
+/* FLOAT32/FLOAT64: moved verbatim as payload, refused as keys and by the
+ * cascaded codec */
+inline constexpr bool is_floating(data_type t)
+{
+  return t.id() == type_id::FLOAT32 || t.id() == type_id::FLOAT64;
+}
+/* integer rep widened to the engine's int64 key by zero extension (every
+ * other integer rep is sign-extended; UINT64 is reinterpreted) */
+inline constexpr bool is_unsigned_rep(data_type t)
+{
+  return t.id() == type_id::UINT8 || t.id() == type_id::UINT16 ||
+         t.id() == type_id::UINT32 || t.id() == type_id::UINT64 ||
+         t.id() == type_id::BOOL8;
+}
+/* fixed-width integer rep: a valid join/shuffle key */
+inline constexpr bool is_integer_rep(data_type t) { return size_of(t) > 0 && !is_floating(t); }
+/* types the cascaded codec takes (the reference declares it for the 8
+ * signed/unsigned integer types; chrono reps ride their integer rep here) */
+inline constexpr bool is_cascaded_supported(data_type t)
+{
+  return is_integer_rep(t) && t.id() != type_id::BOOL8;
+}
 
 /* mirrors cudf::hash_id as used by shuffle_on.hpp:49 */
 enum class hash_id : int32_t { HASH_IDENTITY = 0, HASH_MURMUR3 = 1 };
