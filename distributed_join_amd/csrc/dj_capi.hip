@@ -289,23 +289,25 @@ struct BucketScratch {
   int* any_overflow;           // int[1]
 };
 
-BucketScratch carve_bucket_scratch(void* base, int64_t ln, int64_t rn, int B)
+/* THE list of the bucket join's scratch allocations, each rounded up to 256
+ * bytes: carves them from `base` and returns how many bytes they span. A
+ * null base only measures (the pointers come out null). */
+static size_t bucket_scratch_layout(void* base, int64_t ln, int64_t rn, int B, BucketScratch& s)
 {
   const int PA = dj::bucket_groups_for(B);
   const int64_t maxn = ln > rn ? ln : rn;
   const bool slack = bucket_slack_mode(ln, rn, B);
   const size_t lrows = slack ? (size_t)B * dj::slack_capB(ln, B) : (size_t)ln;
   const size_t rrows = slack ? (size_t)B * dj::slack_capB(rn, B) : (size_t)rn;
-  char* p = (char*)base;
+  size_t off = 0;
   auto take = [&](size_t bytes) {
-    void* r = p;
-    p += (bytes + 255) & ~(size_t)255;
+    void* r = base ? (char*)base + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
     return r;
   };
-  BucketScratch s;
   s.lpairs = (longlong2*)take(lrows * 16);
   s.rpairs = (longlong2*)take(rrows * 16);
-  s.tmp_pairs = (longlong2*)take((size_t)(PA * dj::slack_capA(maxn, PA)) * 16);
+  s.tmp_pairs = (longlong2*)take((size_t)(PA * dj::slack_capA(maxn, PA)) * 16);  // >= maxn
   s.tmp_pairs2 = slack ? (longlong2*)take((size_t)(PA * dj::slack_capA(maxn, PA)) * 16)
                        : nullptr;  // pair-launch partition needs both live
   s.loff = (int64_t*)take((size_t)(B + 1) * 8);
@@ -318,6 +320,13 @@ BucketScratch carve_bucket_scratch(void* base, int64_t ln, int64_t rn, int B)
   s.totals = (uint32_t*)take((size_t)PA * 4);
   s.flags = (uint32_t*)take((size_t)B * 4);
   s.any_overflow = (int*)take(16);
+  return off;
+}
+
+BucketScratch carve_bucket_scratch(void* base, int64_t ln, int64_t rn, int B)
+{
+  BucketScratch s;
+  bucket_scratch_layout(base, ln, rn, B, s);
   return s;
 }
 
@@ -325,29 +334,8 @@ BucketScratch carve_bucket_scratch(void* base, int64_t ln, int64_t rn, int B)
 
 int64_t dj_bucket_join_scratch_bytes(int64_t ln, int64_t rn)
 {
-  int B = dj::bucket_count_for(ln, rn);
-  const int PA = dj::bucket_groups_for(B);
-  const int64_t maxn = ln > rn ? ln : rn;
-  const bool slack = bucket_slack_mode(ln, rn, B);
-  const size_t lrows = slack ? (size_t)B * dj::slack_capB(ln, B) : (size_t)ln;
-  const size_t rrows = slack ? (size_t)B * dj::slack_capB(rn, B) : (size_t)rn;
-  size_t bytes = 0;
-  auto add = [&](size_t b) { bytes += (b + 255) & ~(size_t)255; };
-  add(lrows * 16);
-  add(rrows * 16);
-  add((size_t)(PA * dj::slack_capA(maxn, PA)) * 16);  // pass-A slack staging (>= maxn)
-  if (slack) add((size_t)(PA * dj::slack_capA(maxn, PA)) * 16);  // second table (pair launch)
-  add((size_t)(B + 1) * 8);
-  add((size_t)(B + 1) * 8);
-  const size_t Bpad = ((size_t)B + 3) & ~(size_t)3;
-  add(Bpad * 4);
-  add(Bpad * 4);
-  add((size_t)(PA + 1) * 8);
-  add((size_t)dj::kBucketBlocks * PA * 4);
-  add((size_t)PA * 4);
-  add((size_t)B * 4);
-  add(16);
-  return (int64_t)bytes;
+  BucketScratch unused;
+  return (int64_t)bucket_scratch_layout(nullptr, ln, rn, dj::bucket_count_for(ln, rn), unused);
 }
 
 /* enqueue-only core: all kernels stream-ordered, no host syncs. The skew

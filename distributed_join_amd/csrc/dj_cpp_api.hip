@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <iostream>
 #include <map>
@@ -182,7 +183,7 @@ void sync_streams()
 /* fused multi-column key: h_i = chain of mix64 over the key tuple — the
  * single-key engine then partitions/joins on h as if it were the key, and
  * the caller filters hash-collision false positives against the real
- * columns afterwards (local_inner_join_multi). DJ_TEST_WEAK_FUSE collapses
+ * columns afterwards (local_inner_join). DJ_TEST_WEAK_FUSE collapses
  * h to 4 bits so tests can exercise that filter deterministically. */
 __global__ void fuse_keys_kernel(const int64_t* __restrict__ c0, const int64_t* __restrict__ c1,
                                  const int64_t* __restrict__ c2, const int64_t* __restrict__ c3,
@@ -283,14 +284,47 @@ DBuf fuse_keys(cudf::table_view t, std::vector<cudf::size_type> const& on, hipSt
   return out;
 }
 
-const int64_t* key_as_i64(cudf::column_view col, DBuf& tmp)
+/* the engine's int64 view of an integer-rep key column: the column itself
+ * when it is 64-bit, else widened on `st` into `dst` (col.size() int64s the
+ * caller allocated — nothing is allocated here) */
+const int64_t* key_as_i64(cudf::column_view col, int64_t* dst, hipStream_t st)
 {
   const int kind = key_kind(col.type());
   if (kind == dj::kKeyI64) return col.head<int64_t>();
-  tmp = DBuf((size_t)col.size() * 8);
-  hipLaunchKernelGGL(widen_key_kernel, dim3(grid_for_n(col.size())), dim3(kBlock), 0,
-                     dj_rt_stream(), col.head<void>(), kind, (int64_t)col.size(), tmp.i64());
-  return tmp.i64();
+  hipLaunchKernelGGL(widen_key_kernel, dim3(grid_for_n(col.size())), dim3(kBlock), 0, st,
+                     col.head<void>(), kind, (int64_t)col.size(), dst);
+  return dst;
+}
+
+/* same on the compute stream, allocating `tmp` when the column needs widening */
+const int64_t* key_as_i64(cudf::column_view col, DBuf& tmp)
+{
+  if (key_kind(col.type()) != dj::kKeyI64) tmp = DBuf((size_t)col.size() * 8);
+  return key_as_i64(col, tmp.i64(), dj_rt_stream());
+}
+
+/* a table view over two INT64 device arrays */
+cudf::table_view view_i64_pair(const void* c0, const void* c1, int64_t n)
+{
+  const cudf::data_type i64(cudf::type_id::INT64);
+  return cudf::table_view({cudf::column_view(i64, (cudf::size_type)n, c0),
+                           cudf::column_view(i64, (cudf::size_type)n, c1)});
+}
+
+/* the hot shape: exactly two INT64 columns, one of them the key */
+bool is_i64_pair(cudf::table_view t, cudf::size_type key_col)
+{
+  return t.num_columns() == 2 && (key_col == 0 || key_col == 1) &&
+         t.column(0).type().id() == cudf::type_id::INT64 &&
+         t.column(1).type().id() == cudf::type_id::INT64;
+}
+
+/* both sides of a join have it with the key in front: the engine's four
+ * outputs then ARE the result columns (payloads travel through the join) */
+bool joins_i64_pairs(cudf::table_view left, cudf::table_view right, cudf::size_type left_key,
+                     cudf::size_type right_key)
+{
+  return left_key == 0 && right_key == 0 && is_i64_pair(left, 0) && is_i64_pair(right, 0);
 }
 
 void validate_compression(std::vector<ColumnCompressionOptions> const& opts)
@@ -1350,9 +1384,7 @@ PartitionedTable partition_table(cudf::table_view in, cudf::size_type key_col, i
   DBuf scratch(dj::hash_partition_scratch_bytes(n, nparts));
   DBuf d_off((size_t)(nparts + 1) * 8);
 
-  const bool fast2 = ext_keys == nullptr && in.num_columns() == 2 &&
-                     in.column(0).type().id() == cudf::type_id::INT64 &&
-                     in.column(1).type().id() == cudf::type_id::INT64;
+  const bool fast2 = ext_keys == nullptr && is_i64_pair(in, key_col);
 
   std::vector<std::unique_ptr<cudf::column>> cols;
   if (fast2)
@@ -1394,242 +1426,212 @@ PartitionedTable partition_table(cudf::table_view in, cudf::size_type key_col, i
   return r;
 }
 
-/* local inner join of two tables via the bucketed-LDS engine; returns
- * left-cols + right-cols with keys duplicated, row order unspecified */
-/* multi-key collision filter: keep (li, ri) pairs whose REAL key tuples are
- * equal (the bucket join matched on the fused hash; unequal tuples sharing a
- * fused value are hash collisions to drop). Output order is unspecified
- * (atomic append), as the join's own output order already is. */
-__global__ void filter_tuple_matches_kernel(
-  const int64_t* __restrict__ lc0, const int64_t* __restrict__ lc1,
-  const int64_t* __restrict__ lc2, const int64_t* __restrict__ lc3,
-  const int64_t* __restrict__ rc0, const int64_t* __restrict__ rc1,
-  const int64_t* __restrict__ rc2, const int64_t* __restrict__ rc3, uint32_t lkinds,
-  uint32_t rkinds /*4 bits per col: dj::kKey* */, int nk, const int64_t* __restrict__ li, const int64_t* __restrict__ ri,
-  int64_t n, int64_t* __restrict__ out_li, int64_t* __restrict__ out_ri,
-  unsigned long long* __restrict__ count)
+/* the placement step of shuffle_on: the rows of `input` grouped into nparts
+ * contiguous ranges by the hash of their key. Multi-column keys, and any
+ * STRING key, place on the fused key chain (our spec, dj_hash.h —
+ * MurmurHash3 placement is parity-unpinned) */
+PartitionedTable place_rows(cudf::table_view input, std::vector<cudf::size_type> const& on,
+                            int nparts, int hash_fn, uint32_t seed)
 {
-  const int64_t* lc[4] = {lc0, lc1, lc2, lc3};
-  const int64_t* rc[4] = {rc0, rc1, rc2, rc3};
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    const int64_t a = li[i], b = ri[i];
-    bool eq = true;
-    for (int c = 0; c < nk; c++) {
-      int64_t lv = dj::load_key_i64(lc[c], (int)((lkinds >> (4 * c)) & 0xF), a);
-      int64_t rv = dj::load_key_i64(rc[c], (int)((rkinds >> (4 * c)) & 0xF), b);
-      if (lv != rv) {
-        eq = false;
-        break;
-      }
-    }
-    if (eq) {
-      unsigned long long pos = atomicAdd(count, 1ull);
-      out_li[pos] = a;
-      out_ri[pos] = b;
-    }
+  DBuf fused;
+  const bool str_key = any_string_key(input, on);
+  if (on.size() > 1 || str_key) {
+    DJ_CHECK_ERROR(hash_fn != DJ_HASH_IDENTITY || !str_key,
+                   "identity-hash shuffle is not defined for STRING key columns "
+                   "(cuDF has no identity hash for strings either); use HASH_MURMUR3");
+    DJ_CHECK_ERROR(hash_fn != DJ_HASH_IDENTITY,
+                   "identity-hash shuffle requires a single key column");
+    fused = fuse_keys(input, on, dj_rt_stream());
   }
+  return partition_table(input, on[0], nparts, hash_fn, seed, fused.p ? fused.i64() : nullptr);
 }
 
-std::unique_ptr<cudf::table> local_inner_join(cudf::table_view left, cudf::table_view right,
-                                              cudf::size_type left_on, cudf::size_type right_on)
+/* what one bucket join leaves on the device besides its rows: the match
+ * counter and the engine's two flags, in one block so that a single 16-byte
+ * copy reads them back */
+struct JoinMeta {
+  int64_t count;     // matches found (may exceed the capacity written)
+  int error;         // sentinel (-1) keys seen and skipped
+  int any_overflow;  // skewed buckets skipped
+};
+static_assert(sizeof(JoinMeta) == 16 && offsetof(JoinMeta, count) == 0 &&
+                offsetof(JoinMeta, error) == 8 && offsetof(JoinMeta, any_overflow) == 12,
+              "JoinMeta is read back from the device as one 16-byte block");
+
+/* engine outputs of one join, `cap` rows each: o0/o2 the joined key values
+ * (left/right), o1/o3 the payloads — source row indices unless the tables
+ * are int64 pairs (joins_i64_pairs) */
+struct JoinOut {
+  DBuf o0, o1, o2, o3, meta;
+  int64_t cap{0};
+  JoinOut() = default;
+  explicit JoinOut(int64_t cap_)
+    : o0((size_t)cap_ * 8),
+      o1((size_t)cap_ * 8),
+      o2((size_t)cap_ * 8),
+      o3((size_t)cap_ * 8),
+      meta(sizeof(JoinMeta)),
+      cap(cap_)
+  {
+  }
+  /* first-try capacity for rn probe rows; the engine counts every match but
+   * writes only the first cap, so a count above it means redo */
+  static int64_t default_cap(int64_t rn) { return std::max<int64_t>(rn + (rn >> 3), 1024); }
+  int64_t* counter() { return &((JoinMeta*)meta.p)->count; }
+  int* error() { return &((JoinMeta*)meta.p)->error; }
+  int* any_overflow() { return &((JoinMeta*)meta.p)->any_overflow; }
+  void clear(hipStream_t st) { DJ_HIP_CALL(hipMemsetAsync(meta.p, 0, sizeof(JoinMeta), st)); }
+};
+
+/* the bucketed-LDS engine with its capacity retry: rerun at the exact size
+ * when the matches outnumber the first-try capacity. Host-synchronous. */
+std::pair<JoinOut, int64_t> run_bucket_join(const int64_t* lk, const int64_t* lp, int64_t ln,
+                                            const int64_t* rk, const int64_t* rp, int64_t rn)
 {
   hipStream_t st = dj_rt_stream();
-  const int64_t ln = left.num_rows(), rn = right.num_rows();
-  const cudf::size_type ncl = left.num_columns(), ncr = right.num_columns();
-
-  const bool fast2 = ncl == 2 && ncr == 2 && left_on == 0 && right_on == 0 &&
-                     left.column(0).type().id() == cudf::type_id::INT64 &&
-                     left.column(1).type().id() == cudf::type_id::INT64 &&
-                     right.column(0).type().id() == cudf::type_id::INT64 &&
-                     right.column(1).type().id() == cudf::type_id::INT64;
-
-  auto empty_col = [&](cudf::column_view v) {
-    if (v.type().id() == cudf::type_id::STRING)
-      return std::make_unique<cudf::column>((cudf::size_type)0, (int64_t)0);
-    return std::make_unique<cudf::column>(v.type(), (cudf::size_type)0);
-  };
-  auto make_empty = [&]() {
-    std::vector<std::unique_ptr<cudf::column>> cols;
-    for (cudf::size_type c = 0; c < ncl; c++) cols.push_back(empty_col(left.column(c)));
-    for (cudf::size_type c = 0; c < ncr; c++) cols.push_back(empty_col(right.column(c)));
-    return std::make_unique<cudf::table>(std::move(cols));
-  };
-  if (ln == 0 || rn == 0) return make_empty();  // distributed_join.cpp:76-83
-
-  DBuf lkey_tmp, rkey_tmp;
-  const int64_t* lk = key_as_i64(left.column(left_on), lkey_tmp);
-  const int64_t* rk = key_as_i64(right.column(right_on), rkey_tmp);
-  const int64_t* lp;
-  const int64_t* rp;
-  if (fast2) {
-    lp = left.column(1).head<int64_t>();
-    rp = right.column(1).head<int64_t>();
-  } else {
-    /* general path payload = row index; the partition kernels synthesize it
-     * (pay == nullptr -> i), so no iota arrays to materialize or re-read
-     * (2.4 GB/step at the TPC-H shape) */
-    lp = nullptr;
-    rp = nullptr;
-  }
-
   DBuf scratch((size_t)dj_bucket_join_scratch_bytes(ln, rn));
-  DBuf d_err(16), d_cnt(16);
-  int64_t cap = std::max<int64_t>(rn + (rn >> 3), 1024);
+  int64_t cap = JoinOut::default_cap(rn);
   for (;;) {
-    DBuf o0((size_t)cap * 8), o1((size_t)cap * 8), o2((size_t)cap * 8), o3((size_t)cap * 8);
-    DJ_HIP_CALL(hipMemsetAsync(d_err.p, 0, 4, st));
-    DJ_HIP_CALL(hipMemsetAsync(d_cnt.p, 0, 8, st));
-    dj_bucket_local_join(lk, lp, ln, rk, rp, rn, o0.i64(), o1.i64(), o2.i64(), o3.i64(), cap,
-                         d_cnt.i64(), (int*)d_err.p, scratch.p);
-    int64_t nout = 0;
-    int err = 0;
-    DJ_HIP_CALL(hipMemcpyAsync(&nout, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
-    DJ_HIP_CALL(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, st));
+    JoinOut out(cap);
+    out.clear(st);
+    dj_bucket_local_join(lk, lp, ln, rk, rp, rn, out.o0.i64(), out.o1.i64(), out.o2.i64(),
+                         out.o3.i64(), cap, out.counter(), out.error(), scratch.p);
+    JoinMeta m;
+    DJ_HIP_CALL(hipMemcpyAsync(&m, out.meta.p, sizeof(m), hipMemcpyDeviceToHost, st));
     DJ_HIP_CALL(hipStreamSynchronize(st));
-    DJ_CHECK_ERROR(err == 0, "join: sentinel flag not cleared by the bucket path");
-    if (nout > cap) {
-      cap = nout;
-      continue;
-    }
-    /* assemble output table */
-    std::vector<std::unique_ptr<cudf::column>> cols;
-    if (fast2) {
-      cols.push_back(std::make_unique<cudf::column>(cudf::data_type(cudf::type_id::INT64),
-                                                    (cudf::size_type)nout, o0.p));
-      o0.p = nullptr;
-      cols.push_back(std::make_unique<cudf::column>(cudf::data_type(cudf::type_id::INT64),
-                                                    (cudf::size_type)nout, o1.p));
-      o1.p = nullptr;
-      cols.push_back(std::make_unique<cudf::column>(cudf::data_type(cudf::type_id::INT64),
-                                                    (cudf::size_type)nout, o2.p));
-      o2.p = nullptr;
-      cols.push_back(std::make_unique<cudf::column>(cudf::data_type(cudf::type_id::INT64),
-                                                    (cudf::size_type)nout, o3.p));
-      o3.p = nullptr;
-    } else {
-      /* general: o1/o3 hold source row indices; gather every column —
-       * EXCEPT the key columns, whose joined values already sit in o0/o2 */
-      gather_table_columns(left, o1, nout, left_on, &o0, cols, st);
-      gather_table_columns(right, o3, nout, right_on, &o2, cols, st);
-      DJ_HIP_CALL(hipStreamSynchronize(st));
-    }
-    return std::make_unique<cudf::table>(std::move(cols));
+    DJ_CHECK_ERROR(m.error == 0, "join: sentinel flag not cleared by the bucket path");
+    if (m.count <= cap) return {std::move(out), m.count};
+    cap = m.count;
   }
 }
 
-/* multi-column-key local inner join: bucket-join on the fused key chain
- * (fuse_keys) with row-index payloads, drop fused-hash collisions against
- * the real columns, then gather all output columns — the single-key engine
- * does the heavy lifting; only placement/equality semantics widen.
- * (Reference: cudf::inner_join on arbitrary left_on/right_on,
- * distributed_join.cpp:71-132.) */
-std::unique_ptr<cudf::table> local_inner_join_multi(cudf::table_view left,
-                                                    cudf::table_view right,
-                                                    std::vector<cudf::size_type> const& lon,
-                                                    std::vector<cudf::size_type> const& ron)
+/* the empty table with a join's output schema: left's columns, then right's */
+std::unique_ptr<cudf::table> empty_join_result(cudf::table_view left, cudf::table_view right)
+{
+  std::vector<std::unique_ptr<cudf::column>> cols;
+  for (cudf::table_view const& t : {left, right})
+    for (cudf::size_type c = 0; c < t.num_columns(); c++) {
+      if (is_string(t.column(c)))
+        cols.push_back(std::make_unique<cudf::column>((cudf::size_type)0, (int64_t)0));
+      else
+        cols.push_back(std::make_unique<cudf::column>(t.column(c).type(), (cudf::size_type)0));
+    }
+  return std::make_unique<cudf::table>(std::move(cols));
+}
+
+/* the first n rows of the engine's four outputs as four INT64 columns */
+std::unique_ptr<cudf::table> adopt_i64x4(JoinOut& out, int64_t n)
+{
+  std::vector<std::unique_ptr<cudf::column>> cols;
+  for (DBuf* d : {&out.o0, &out.o1, &out.o2, &out.o3}) {
+    cols.push_back(std::make_unique<cudf::column>(cudf::data_type(cudf::type_id::INT64),
+                                                  (cudf::size_type)n, d->p));
+    d->p = nullptr;
+  }
+  return std::make_unique<cudf::table>(std::move(cols));
+}
+
+/* nout joined rows -> left-cols + right-cols. int64 pairs adopt the engine's
+ * outputs as they are. Otherwise o1/o3 hold source row indices and every
+ * column is gathered — EXCEPT a single integer key column (left_key /
+ * right_key >= 0), whose joined values already sit in o0/o2 and are adopted
+ * or narrowed instead (see gather_table_columns) */
+std::unique_ptr<cudf::table> assemble_join_output(cudf::table_view left, cudf::table_view right,
+                                                  JoinOut& out, int64_t nout,
+                                                  cudf::size_type left_key,
+                                                  cudf::size_type right_key)
+{
+  if (joins_i64_pairs(left, right, left_key, right_key)) return adopt_i64x4(out, nout);
+  hipStream_t st = dj_rt_stream();
+  std::vector<std::unique_ptr<cudf::column>> cols;
+  gather_table_columns(left, out.o1, nout, left_key, &out.o0, cols, st);
+  gather_table_columns(right, out.o3, nout, right_key, &out.o2, cols, st);
+  DJ_HIP_CALL(hipStreamSynchronize(st));
+  return std::make_unique<cudf::table>(std::move(cols));
+}
+
+dj::TupleKeyCol tuple_key_col(cudf::column_view col)
+{
+  dj::TupleKeyCol d{};
+  d.data = col.head<void>();
+  d.chars = (const uint8_t*)col.chars();
+  d.kind = is_string(col) ? (int)dj::kKeyStr : key_kind(col.type());
+  return d;
+}
+
+/* local inner join of two tables via the bucketed-LDS engine; returns
+ * left-cols + right-cols with keys duplicated, row order unspecified.
+ * A single integer key column is the engine's key as it is (widened when
+ * narrow). Composite keys, and STRING keys even alone, bucket-join on the
+ * fused key chain (fuse_keys: the row hash stands in for a string) with
+ * row-index payloads, then drop fused-hash collisions against the real
+ * columns — the single-key engine does the heavy lifting; only
+ * placement/equality semantics widen. (Reference: cudf::inner_join on
+ * arbitrary left_on/right_on, distributed_join.cpp:71-132.) */
+std::unique_ptr<cudf::table> local_inner_join(cudf::table_view left, cudf::table_view right,
+                                              std::vector<cudf::size_type> const& lon,
+                                              std::vector<cudf::size_type> const& ron)
 {
   DJ_CHECK_ERROR(lon.size() == ron.size(), "left_on/right_on must have equal length");
-  /* STRING keys (even a single one) join on the fused chain too: the row
-   * hash stands in for the string, the filter compares the real bytes, and
-   * the key STRING columns are gathered into the output on both sides */
   bool str_keys = false;
   for (size_t c = 0; c < lon.size(); c++) {
     const bool ls = is_string(left.column(lon[c])), rs = is_string(right.column(ron[c]));
     DJ_CHECK_ERROR(ls == rs, "a STRING key column must pair with a STRING key column");
     str_keys |= ls;
   }
-  if (lon.size() == 1 && !str_keys) return local_inner_join(left, right, lon[0], ron[0]);
+  const bool fused = lon.size() > 1 || str_keys;
   hipStream_t st = dj_rt_stream();
   const int64_t ln = left.num_rows(), rn = right.num_rows();
-  const cudf::size_type ncl = left.num_columns(), ncr = right.num_columns();
+  if (ln == 0 || rn == 0) return empty_join_result(left, right);  // distributed_join.cpp:76-83
 
-  auto empty_col = [&](cudf::column_view v) {
-    if (v.type().id() == cudf::type_id::STRING)
-      return std::make_unique<cudf::column>((cudf::size_type)0, (int64_t)0);
-    return std::make_unique<cudf::column>(v.type(), (cudf::size_type)0);
-  };
-  auto make_empty = [&]() {
-    std::vector<std::unique_ptr<cudf::column>> cols;
-    for (cudf::size_type c = 0; c < ncl; c++) cols.push_back(empty_col(left.column(c)));
-    for (cudf::size_type c = 0; c < ncr; c++) cols.push_back(empty_col(right.column(c)));
-    return std::make_unique<cudf::table>(std::move(cols));
-  };
-  if (ln == 0 || rn == 0) return make_empty();
+  /* the output's key columns: known only for a single integer key (a fused
+   * key's columns are gathered like any other) */
+  const cudf::size_type left_key = fused ? -1 : lon[0], right_key = fused ? -1 : ron[0];
+  DBuf lkey_tmp, rkey_tmp;
+  const int64_t* lk;
+  const int64_t* rk;
+  if (fused) {
+    lkey_tmp = fuse_keys(left, lon, st);
+    rkey_tmp = fuse_keys(right, ron, st);
+    lk = lkey_tmp.i64();
+    rk = rkey_tmp.i64();
+  } else {
+    lk = key_as_i64(left.column(left_key), lkey_tmp);
+    rk = key_as_i64(right.column(right_key), rkey_tmp);
+  }
+  /* general path payload = row index; the partition kernels synthesize it
+   * (pay == nullptr -> i), so no iota arrays to materialize or re-read
+   * (2.4 GB/step at the TPC-H shape) */
+  const bool pairs = joins_i64_pairs(left, right, left_key, right_key);
+  const int64_t* lp = pairs ? left.column(1).head<int64_t>() : nullptr;
+  const int64_t* rp = pairs ? right.column(1).head<int64_t>() : nullptr;
 
-  DBuf lfused = fuse_keys(left, lon, st);
-  DBuf rfused = fuse_keys(right, ron, st);
-
-  DBuf scratch((size_t)dj_bucket_join_scratch_bytes(ln, rn));
-  DBuf d_err(16), d_cnt(16);
-  int64_t cap = std::max<int64_t>(rn + (rn >> 3), 1024);
-  for (;;) {
-    DBuf o0((size_t)cap * 8), o1((size_t)cap * 8), o2((size_t)cap * 8), o3((size_t)cap * 8);
-    DJ_HIP_CALL(hipMemsetAsync(d_err.p, 0, 4, st));
-    DJ_HIP_CALL(hipMemsetAsync(d_cnt.p, 0, 8, st));
-    dj_bucket_local_join(lfused.i64(), nullptr, ln, rfused.i64(), nullptr, rn, o0.i64(),
-                         o1.i64(), o2.i64(), o3.i64(), cap, d_cnt.i64(), (int*)d_err.p,
-                         scratch.p);
-    int64_t nout = 0;
-    int err = 0;
-    DJ_HIP_CALL(hipMemcpyAsync(&nout, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
-    DJ_HIP_CALL(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, st));
-    DJ_HIP_CALL(hipStreamSynchronize(st));
-    DJ_CHECK_ERROR(err == 0, "join: sentinel flag not cleared by the bucket path");
-    if (nout > cap) {
-      cap = nout;
-      continue;
-    }
-    /* drop fused-hash collisions against the real key columns */
-    const int64_t* lptr[4] = {nullptr, nullptr, nullptr, nullptr};
-    const int64_t* rptr[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t lkinds = 0, rkinds = 0;
+  auto joined = run_bucket_join(lk, lp, ln, rk, rp, rn);
+  JoinOut& out = joined.first;
+  int64_t nout = joined.second;
+  if (fused) {
+    /* collision filter: keep the (li, ri) pairs whose REAL key tuples are
+     * equal (the bucket join matched on the fused hash; unequal tuples
+     * sharing a fused value are hash collisions to drop). Output order is
+     * unspecified (atomic append), as the join's own output order already is. */
+    dj::TupleKeys tk{};
+    tk.nk = (int)lon.size();
     for (size_t c = 0; c < lon.size(); c++) {
-      lptr[c] = left.column(lon[c]).head<int64_t>();
-      rptr[c] = right.column(ron[c]).head<int64_t>();
-      if (!str_keys) {
-        lkinds |= (uint32_t)key_kind(left.column(lon[c]).type()) << (4 * c);
-        rkinds |= (uint32_t)key_kind(right.column(ron[c]).type()) << (4 * c);
-      }
+      tk.l[c] = tuple_key_col(left.column(lon[c]));
+      tk.r[c] = tuple_key_col(right.column(ron[c]));
     }
     DBuf li2((size_t)std::max<int64_t>(nout, 1) * 8);
     DBuf ri2((size_t)std::max<int64_t>(nout, 1) * 8);
-    DJ_HIP_CALL(hipMemsetAsync(d_cnt.p, 0, 8, st));
-    if (nout > 0 && str_keys) {
-      dj::TupleKeys tk{};
-      tk.nk = (int)lon.size();
-      auto desc = [](cudf::column_view col) {
-        dj::TupleKeyCol d{};
-        d.data = col.head<void>();
-        d.chars = (const uint8_t*)col.chars();
-        d.kind = is_string(col) ? (int)dj::kKeyStr : key_kind(col.type());
-        return d;
-      };
-      for (size_t c = 0; c < lon.size(); c++) {
-        tk.l[c] = desc(left.column(lon[c]));
-        tk.r[c] = desc(right.column(ron[c]));
-      }
-      dj::filter_tuple_matches_mixed(tk, o1.i64(), o3.i64(), nout, li2.i64(), ri2.i64(),
-                                     (unsigned long long*)d_cnt.p, st);
-    } else if (nout > 0) {
-      hipLaunchKernelGGL(filter_tuple_matches_kernel, dim3(grid_for_n(nout)), dim3(kBlock),
-                         0, st, lptr[0], lptr[1], lptr[2], lptr[3], rptr[0], rptr[1],
-                         rptr[2], rptr[3], lkinds, rkinds, (int)lon.size(), o1.i64(), o3.i64(),
-                         nout, li2.i64(), ri2.i64(), (unsigned long long*)d_cnt.p);
-      DJ_HIP_CALL(hipGetLastError());
-    }
-    int64_t m = 0;
-    DJ_HIP_CALL(hipMemcpyAsync(&m, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
+    out.clear(st);
+    dj::filter_tuple_matches_mixed(tk, out.o1.i64(), out.o3.i64(), nout, li2.i64(), ri2.i64(),
+                                   (unsigned long long*)out.counter(), st);
+    DJ_HIP_CALL(hipMemcpyAsync(&nout, out.counter(), 8, hipMemcpyDeviceToHost, st));
     DJ_HIP_CALL(hipStreamSynchronize(st));
-    if (m == 0) return make_empty();
-
-    std::vector<std::unique_ptr<cudf::column>> cols;
-    gather_table_columns(left, li2, m, -1, nullptr, cols, st);
-    gather_table_columns(right, ri2, m, -1, nullptr, cols, st);
-    DJ_HIP_CALL(hipStreamSynchronize(st));
-    return std::make_unique<cudf::table>(std::move(cols));
+    if (nout == 0) return empty_join_result(left, right);
+    out.o1 = std::move(li2);
+    out.o3 = std::move(ri2);
   }
+  return assemble_join_output(left, right, out, nout, left_key, right_key);
 }
 
 /* rebase a part's offsets by a constant and append (STRING concat) */
@@ -1688,6 +1690,54 @@ std::unique_ptr<cudf::table> concat_tables(std::vector<std::unique_ptr<cudf::tab
   }
   DJ_HIP_CALL(hipStreamSynchronize(st));
   return std::make_unique<cudf::table>(std::move(cols));
+}
+
+/* what batch finalisation needs of a pipeline batch; both pipelines' Batch
+ * structs extend it with their own staging */
+struct BatchJoin {
+  std::unique_ptr<AllToAllCommunicator> latoa, ratoa;
+  std::unique_ptr<cudf::table> lrecv, rrecv;  // this rank's share of the batch
+  JoinOut out;                                // its join, enqueued by the pipeline
+};
+
+/* the end of both batched pipelines, once the compute stream has drained:
+ * per batch read the counts, redo the rare failures, assemble the columns;
+ * then concatenate. A batch with an empty side had nothing enqueued and its
+ * meta block is all zero. The redo goes synchronously through
+ * local_inner_join, whose bucket path joins sentinel (-1) keys out-of-band
+ * (neg1_cross_join), re-joins skewed buckets via the global-table fallback
+ * and sizes the output exactly. The flags are looked at BEFORE the count:
+ * the enqueued join skips -1 keys and oversized buckets, so its count can be
+ * 0 while the redo still finds rows. */
+template <class Batch>
+std::unique_ptr<cudf::table> finalize_batches(std::vector<Batch>& batches,
+                                              cudf::size_type left_key,
+                                              cudf::size_type right_key, bool report_timing,
+                                              int rank)
+{
+  std::vector<std::unique_ptr<cudf::table>> results;
+  for (BatchJoin& bt : batches) {
+    const cudf::table_view l = bt.lrecv->view(), r = bt.rrecv->view();
+    JoinMeta meta;
+    DJ_HIP_CALL(hipMemcpy(&meta, bt.out.meta.p, sizeof(meta), hipMemcpyDeviceToHost));
+    if (l.num_rows() == 0 || r.num_rows() == 0)
+      results.push_back(empty_join_result(l, r));
+    else if (meta.error || meta.any_overflow || meta.count > bt.out.cap)
+      results.push_back(local_inner_join(l, r, {left_key}, {right_key}));
+    else if (meta.count == 0)
+      results.push_back(empty_join_result(l, r));
+    else
+      results.push_back(assemble_join_output(l, r, bt.out, meta.count, left_key, right_key));
+  }
+  const auto t_cat0 = std::chrono::steady_clock::now();
+  auto result = concat_tables(results);
+  if (report_timing && batches.size() > 1)
+    std::cout << "Rank " << rank << ": concatenation takes "
+              << std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() -
+                                                           t_cat0)
+                   .count()
+              << "ms" << std::endl;
+  return result;
 }
 
 }  // namespace
@@ -1773,31 +1823,19 @@ std::unique_ptr<cudf::table> distributed_inner_join_fused(
     DJ_HIP_CALL(hipStreamSynchronize(st));
   }
 
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  cudf::table_view lpart_view({column_view(data_type(type_id::INT64), (cudf::size_type)ln,
-                                           lkp.p),
-                               column_view(data_type(type_id::INT64), (cudf::size_type)ln,
-                                           lpp.p)});
-  cudf::table_view rpart_view({column_view(data_type(type_id::INT64), (cudf::size_type)rn,
-                                           rkp.p),
-                               column_view(data_type(type_id::INT64), (cudf::size_type)rn,
-                                           rpp.p)});
+  cudf::table_view lpart_view = view_i64_pair(lkp.p, lpp.p, ln);
+  cudf::table_view rpart_view = view_i64_pair(rkp.p, rpp.p, rn);
 
-  struct Batch {
-    std::unique_ptr<AllToAllCommunicator> latoa, ratoa;
-    std::unique_ptr<cudf::table> lrecv, rrecv;
+  struct Batch : BatchJoin {
     std::vector<std::vector<int64_t>> lsub_recv, rsub_recv;  // [G][PA]
     DBuf lseg, rseg;       // device [G][PA+1]
     DBuf lgb, rgb;         // device [PA+1] group bases
     DBuf lpairs, rpairs;   // bucketed pairs
     DBuf loff, roff;       // int64[B+1]
     DBuf flags;            // u32[B]
-    DBuf o0, o1, o2, o3, meta;
     int F{0};
     int join_slots{2048};
-    int64_t cap{0}, lrows{0}, rrows{0};
+    int64_t lrows{0}, rrows{0};
   };
   std::vector<Batch> batches(od);
 
@@ -1876,12 +1914,7 @@ std::unique_ptr<cudf::table> distributed_inner_join_fused(
     bt.loff = DBuf((size_t)(B + 1) * 8);
     bt.roff = DBuf((size_t)(B + 1) * 8);
     bt.flags = DBuf((size_t)B * 4);
-    bt.cap = std::max<int64_t>(bt.rrows + (bt.rrows >> 3), 1024);
-    bt.o0 = DBuf((size_t)bt.cap * 8);
-    bt.o1 = DBuf((size_t)bt.cap * 8);
-    bt.o2 = DBuf((size_t)bt.cap * 8);
-    bt.o3 = DBuf((size_t)bt.cap * 8);
-    bt.meta = DBuf(16);
+    bt.out = JoinOut(JoinOut::default_cap(bt.rrows));
   }
 
   /* pipeline: comm(b) then enqueue passB+join(b); comm(b+1) overlaps */
@@ -1889,7 +1922,7 @@ std::unique_ptr<cudf::table> distributed_inner_join_fused(
     Batch& bt = batches[b];
     bt.latoa->launch_communication(bt.lrecv->mutable_view(), report_timing, pinned);
     bt.ratoa->launch_communication(bt.rrecv->mutable_view(), report_timing, pinned);
-    DJ_HIP_CALL(hipMemsetAsync(bt.meta.p, 0, 16, st));
+    bt.out.clear(st);
     if (bt.lrows == 0 || bt.rrows == 0) continue;
     int64_t B = (int64_t)PA * bt.F;
     DJ_HIP_CALL(hipMemsetAsync(bt.flags.p, 0, (size_t)B * 4, st));
@@ -1906,51 +1939,13 @@ std::unique_ptr<cudf::table> distributed_inner_join_fused(
       dj_timing::Scope t(DJ_PHASE_JOIN_FUSED, st);
       dj::lds_join((const longlong2*)bt.lpairs.p, bt.loff.i64(),
                    (const longlong2*)bt.rpairs.p, bt.roff.i64(), (int)B, bt.join_slots,
-                   bt.o0.i64(), bt.o1.i64(), bt.o2.i64(), bt.o3.i64(), bt.cap, bt.meta.i64(),
-                   (uint32_t*)bt.flags.p, (int*)((char*)bt.meta.p + 12),
-                   (int*)((char*)bt.meta.p + 8), st);
+                   bt.out.o0.i64(), bt.out.o1.i64(), bt.out.o2.i64(), bt.out.o3.i64(),
+                   bt.out.cap, bt.out.counter(), (uint32_t*)bt.flags.p, bt.out.any_overflow(),
+                   bt.out.error(), st);
     }
   }
   DJ_HIP_CALL(hipStreamSynchronize(st));
-
-  /* finalize */
-  std::vector<std::unique_ptr<cudf::table>> results;
-  for (int b = 0; b < od; b++) {
-    Batch& bt = batches[b];
-    struct {
-      int64_t count;
-      int error;
-      int any_overflow;
-    } meta;
-    DJ_HIP_CALL(hipMemcpy(&meta, bt.meta.p, 16, hipMemcpyDeviceToHost));
-    if (bt.lrows == 0 || bt.rrows == 0) {
-      std::vector<std::unique_ptr<cudf::column>> cols;
-      for (int c = 0; c < 4; c++)
-        cols.push_back(std::make_unique<cudf::column>(data_type(type_id::INT64),
-                                                      (cudf::size_type)0));
-      results.push_back(std::make_unique<cudf::table>(std::move(cols)));
-      continue;
-    }
-    /* meta.error = sentinel (-1) keys seen: redo through local_inner_join,
-     * whose bucket path joins them out-of-band (neg1_cross_join) */
-    if (meta.error || meta.any_overflow || meta.count > bt.cap) {
-      results.push_back(local_inner_join(bt.lrecv->view(), bt.rrecv->view(), 0, 0));
-      continue;
-    }
-    std::vector<std::unique_ptr<cudf::column>> cols;
-    auto adopt = [&](DBuf& d) {
-      auto col = std::make_unique<cudf::column>(data_type(type_id::INT64),
-                                                (cudf::size_type)meta.count, d.p);
-      d.p = nullptr;
-      return col;
-    };
-    cols.push_back(adopt(bt.o0));
-    cols.push_back(adopt(bt.o1));
-    cols.push_back(adopt(bt.o2));
-    cols.push_back(adopt(bt.o3));
-    results.push_back(std::make_unique<cudf::table>(std::move(cols)));
-  }
-  return concat_tables(results);
+  return finalize_batches(batches, 0, 0, false, communicator->mpi_rank);
 }
 
 }  // namespace
@@ -2011,10 +2006,7 @@ std::unique_ptr<cudf::table> distributed_inner_join(
     left = l_ib->view();
     right = r_ib->view();
   }
-  if (nvl == 1) {
-    if (fused_keys) return local_inner_join_multi(left, right, left_on, right_on);
-    return local_inner_join(left, right, left_on[0], right_on[0]);
-  }
+  if (nvl == 1) return local_inner_join(left, right, left_on, right_on);
 
   if (fused_keys) {
     /* multi-column keys, and STRING keys even alone, take the shuffle +
@@ -2028,7 +2020,7 @@ std::unique_ptr<cudf::table> distributed_inner_join(
     auto rs = shuffle_on(right, right_on, g2, communicator, right_compression_options,
                          cudf::hash_id::HASH_MURMUR3, DJ_SEED_INTRA, report_timing,
                          preallocated_pinned_buffer);
-    return local_inner_join_multi(ls->view(), rs->view(), left_on, right_on);
+    return local_inner_join(ls->view(), rs->view(), left_on, right_on);
   }
 
   const int G = nvl;
@@ -2040,22 +2032,16 @@ std::unique_ptr<cudf::table> distributed_inner_join(
   /* fused wire path for the hot shape (2 x INT64 columns, key at 0):
    * partitions carry the bucket grouping on the wire, removing the separate
    * stable rank partition and bucket pass A */
-  {
-    const bool fast2f = left.num_columns() == 2 && right.num_columns() == 2 &&
-                        left_on[0] == 0 && right_on[0] == 0 &&
-                        left.column(0).type().id() == cudf::type_id::INT64 &&
-                        left.column(1).type().id() == cudf::type_id::INT64 &&
-                        right.column(0).type().id() == cudf::type_id::INT64 &&
-                        right.column(1).type().id() == cudf::type_id::INT64;
-    if (fast2f) {
-      int pa = 1;
-      while (pa * 2 * nparts <= 1024) pa *= 2;
-      if (pa >= 4)
-        return distributed_inner_join_fused(left, right, communicator, group,
-                                            left_compression_options,
-                                            right_compression_options, over_decom_factor, pa,
-                                            report_timing, preallocated_pinned_buffer);
-    }
+  const cudf::size_type left_key = left_on[0], right_key = right_on[0];
+  const bool fast2 = joins_i64_pairs(left, right, left_key, right_key);
+  if (fast2) {
+    int pa = 1;
+    while (pa * 2 * nparts <= 1024) pa *= 2;
+    if (pa >= 4)
+      return distributed_inner_join_fused(left, right, communicator, group,
+                                          left_compression_options, right_compression_options,
+                                          over_decom_factor, pa, report_timing,
+                                          preallocated_pinned_buffer);
   }
 
   /* report_timing mirrors the reference's per-phase prints
@@ -2068,28 +2054,18 @@ std::unique_ptr<cudf::table> distributed_inner_join(
 
   /* rank-level stable partition, seed 12345678 (distributed_join.cpp:211-226) */
   PartitionedTable lpart =
-    partition_table(left, left_on[0], nparts, DJ_HASH_MURMUR3, DJ_SEED_INTRA);
+    partition_table(left, left_key, nparts, DJ_HASH_MURMUR3, DJ_SEED_INTRA);
   PartitionedTable rpart =
-    partition_table(right, right_on[0], nparts, DJ_HASH_MURMUR3, DJ_SEED_INTRA);
+    partition_table(right, right_key, nparts, DJ_HASH_MURMUR3, DJ_SEED_INTRA);
   if (report_timing)
     std::cout << "Rank " << communicator->mpi_rank << ": hash partition takes "
               << ms(t_part0, now()) << "ms" << std::endl;
 
   /* --- pre-phase: size exchanges + every allocation (pool allocs sync the
    * compute stream, so none happen inside the pipeline) --- */
-  const bool fast2 = left.num_columns() == 2 && right.num_columns() == 2 &&
-                     left_on[0] == 0 && right_on[0] == 0 &&
-                     left.column(0).type().id() == cudf::type_id::INT64 &&
-                     left.column(1).type().id() == cudf::type_id::INT64 &&
-                     right.column(0).type().id() == cudf::type_id::INT64 &&
-                     right.column(1).type().id() == cudf::type_id::INT64;
-  struct Batch {
-    std::unique_ptr<AllToAllCommunicator> latoa, ratoa;
-    std::unique_ptr<cudf::table> lrecv, rrecv;
-    DBuf lkw, rkw, liota, riota;  // general-path key widen / row-index payloads
-    DBuf o0, o1, o2, o3;          // engine outputs
-    DBuf meta;                    // counter(8) + error(4) + any_overflow(4)
-    int64_t ln{0}, rn{0}, cap{0};
+  struct Batch : BatchJoin {
+    DBuf lkw, rkw;  // widened keys, where the key column is narrower than 64 bits
+    int64_t ln{0}, rn{0};
   };
   std::vector<Batch> batches(over_decom_factor);
   int64_t max_ln = 1, max_rn = 1;
@@ -2111,18 +2087,11 @@ std::unique_ptr<cudf::table> distributed_inner_join(
     bt.rn = bt.rrecv->num_rows();
     max_ln = std::max(max_ln, bt.ln);
     max_rn = std::max(max_rn, bt.rn);
-    bt.cap = std::max<int64_t>(bt.rn + (bt.rn >> 3), 1024);
-    bt.o0 = DBuf((size_t)bt.cap * 8);
-    bt.o1 = DBuf((size_t)bt.cap * 8);
-    bt.o2 = DBuf((size_t)bt.cap * 8);
-    bt.o3 = DBuf((size_t)bt.cap * 8);
-    bt.meta = DBuf(16);
-    if (!fast2) {
-      if (bt.ln && cudf::size_of(left.column(left_on[0]).type()) < 8)
-        bt.lkw = DBuf((size_t)bt.ln * 8);
-      if (bt.rn && cudf::size_of(right.column(right_on[0]).type()) < 8)
-        bt.rkw = DBuf((size_t)bt.rn * 8);
-    }
+    bt.out = JoinOut(JoinOut::default_cap(bt.rn));
+    if (bt.ln && cudf::size_of(left.column(left_key).type()) < 8)
+      bt.lkw = DBuf((size_t)bt.ln * 8);
+    if (bt.rn && cudf::size_of(right.column(right_key).type()) < 8)
+      bt.rkw = DBuf((size_t)bt.rn * 8);
   }
   DBuf scratch((size_t)dj_bucket_join_scratch_bytes(max_ln, max_rn));
   hipStream_t st = dj_rt_stream();
@@ -2143,37 +2112,20 @@ std::unique_ptr<cudf::table> distributed_inner_join(
     if (report_timing)
       std::cout << "Rank " << communicator->mpi_rank << ": all-to-all communication (batch "
                 << b << ") takes " << ms(t_comm0, now()) << "ms" << std::endl;
-    if (bt.ln == 0 || bt.rn == 0) {
-      DJ_HIP_CALL(hipMemsetAsync(bt.meta.p, 0, 16, st));
-      continue;
-    }
-    const int64_t* lk;
-    const int64_t* rk;
-    const int64_t* lp;
-    const int64_t* rp;
-    if (fast2) {
-      lk = (const int64_t*)bt.lrecv->get_column(0).head();
-      lp = (const int64_t*)bt.lrecv->get_column(1).head();
-      rk = (const int64_t*)bt.rrecv->get_column(0).head();
-      rp = (const int64_t*)bt.rrecv->get_column(1).head();
-    } else {
-      auto widen_or_use = [&](cudf::column_view col, DBuf& w) -> const int64_t* {
-        const int kind = key_kind(col.type());
-        if (kind == dj::kKeyI64) return col.head<int64_t>();
-        hipLaunchKernelGGL(widen_key_kernel, dim3(grid_for_n(col.size())), dim3(kBlock), 0, st,
-                           col.head<void>(), kind, (int64_t)col.size(), w.i64());
-        return w.i64();
-      };
-      lk = widen_or_use(bt.lrecv->view().column(left_on[0]), bt.lkw);
-      rk = widen_or_use(bt.rrecv->view().column(right_on[0]), bt.rkw);
-      lp = nullptr;  // partition kernels synthesize the row-index payload
-      rp = nullptr;
-    }
-    DJ_HIP_CALL(hipMemsetAsync(bt.meta.p, 0, 16, st));
-    dj_bucket_local_join_enqueue(lk, lp, bt.ln, rk, rp, bt.rn, bt.o0.i64(), bt.o1.i64(),
-                                 bt.o2.i64(), bt.o3.i64(), bt.cap, bt.meta.i64(),
-                                 (int*)((char*)bt.meta.p + 8),
-                                 (int*)((char*)bt.meta.p + 12), scratch.p);
+    bt.out.clear(st);
+    if (bt.ln == 0 || bt.rn == 0) continue;
+    const cudf::table_view l = bt.lrecv->view(), r = bt.rrecv->view();
+    /* narrow keys widen into the buffers of the pre-phase; int64 pairs carry
+     * their payloads through the join, every other shape the row index,
+     * which the partition kernels synthesize (pay == nullptr) */
+    const int64_t* lk = key_as_i64(l.column(left_key), bt.lkw.i64(), st);
+    const int64_t* rk = key_as_i64(r.column(right_key), bt.rkw.i64(), st);
+    const int64_t* lp = fast2 ? l.column(1).head<int64_t>() : nullptr;
+    const int64_t* rp = fast2 ? r.column(1).head<int64_t>() : nullptr;
+    dj_bucket_local_join_enqueue(lk, lp, bt.ln, rk, rp, bt.rn, bt.out.o0.i64(),
+                                 bt.out.o1.i64(), bt.out.o2.i64(), bt.out.o3.i64(), bt.out.cap,
+                                 bt.out.counter(), bt.out.error(), bt.out.any_overflow(),
+                                 scratch.p);
   }
   DJ_HIP_CALL(hipStreamSynchronize(st));
   if (report_timing)
@@ -2181,75 +2133,9 @@ std::unique_ptr<cudf::table> distributed_inner_join(
               << ": communication + local join pipeline takes " << ms(t_pipe0, now()) << "ms"
               << std::endl;
 
-  /* --- finalize: counts, rare redo (skew overflow / cap exceeded), column
-   * assembly, concat --- */
-  std::vector<std::unique_ptr<cudf::table>> batch_results;
-  for (int b = 0; b < over_decom_factor; b++) {
-    Batch& bt = batches[b];
-    struct {
-      int64_t count;
-      int error;
-      int any_overflow;
-    } meta;
-    DJ_HIP_CALL(hipMemcpy(&meta, bt.meta.p, 16, hipMemcpyDeviceToHost));
-    if (meta.error) {
-      /* sentinel (-1) keys seen: redo through local_inner_join, whose
-       * bucket path joins them out-of-band (neg1_cross_join) */
-      batch_results.push_back(
-        local_inner_join(bt.lrecv->view(), bt.rrecv->view(), left_on[0], right_on[0]));
-      continue;
-    }
-    if (bt.ln == 0 || bt.rn == 0 || meta.count == 0) {
-      /* empty batch result with the output schema */
-      std::vector<std::unique_ptr<cudf::column>> cols;
-      auto empty_col2 = [&](cudf::column_view v) {
-        if (v.type().id() == cudf::type_id::STRING)
-          return std::make_unique<cudf::column>((cudf::size_type)0, (int64_t)0);
-        return std::make_unique<cudf::column>(v.type(), (cudf::size_type)0);
-      };
-      for (cudf::size_type c = 0; c < left.num_columns(); c++)
-        cols.push_back(empty_col2(left.column(c)));
-      for (cudf::size_type c = 0; c < right.num_columns(); c++)
-        cols.push_back(empty_col2(right.column(c)));
-      batch_results.push_back(std::make_unique<cudf::table>(std::move(cols)));
-      continue;
-    }
-    if (meta.any_overflow || meta.count > bt.cap) {
-      /* rare path: redo this batch synchronously (handles skewed buckets
-       * via the global-table fallback and exact capacity) */
-      batch_results.push_back(
-        local_inner_join(bt.lrecv->view(), bt.rrecv->view(), left_on[0], right_on[0]));
-      continue;
-    }
-    const int64_t nout = meta.count;
-    std::vector<std::unique_ptr<cudf::column>> cols;
-    if (fast2) {
-      auto adopt = [&](DBuf& d) {
-        auto col = std::make_unique<cudf::column>(cudf::data_type(cudf::type_id::INT64),
-                                                  (cudf::size_type)nout, d.p);
-        d.p = nullptr;
-        return col;
-      };
-      cols.push_back(adopt(bt.o0));
-      cols.push_back(adopt(bt.o1));
-      cols.push_back(adopt(bt.o2));
-      cols.push_back(adopt(bt.o3));
-    } else {
-      /* key columns adopt/narrow o0/o2 (joined key values) instead of a
-       * random-line gather — see gather_table_columns */
-      gather_table_columns(bt.lrecv->view(), bt.o1, nout, left_on[0], &bt.o0, cols, st);
-      gather_table_columns(bt.rrecv->view(), bt.o3, nout, right_on[0], &bt.o2, cols, st);
-      DJ_HIP_CALL(hipStreamSynchronize(st));
-    }
-    batch_results.push_back(std::make_unique<cudf::table>(std::move(cols)));
-  }
-  auto t_cat0 = now();
-  auto result = concat_tables(batch_results);
-  if (report_timing && over_decom_factor > 1)
-    std::cout << "Rank " << communicator->mpi_rank << ": concatenation takes "
-              << ms(t_cat0, now()) << "ms" << std::endl;
-  return result;
+  return finalize_batches(batches, left_key, right_key, report_timing, communicator->mpi_rank);
 }
+
 
 /* ------------------------------------------------------------- shuffle_on */
 
@@ -2268,21 +2154,7 @@ std::unique_ptr<cudf::table> shuffle_on(cudf::table_view const& input,
     hash_function == cudf::hash_id::HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3;
   DJ_CHECK_ERROR(on_columns.size() <= 4, "shuffle_on: up to 4 key columns supported");
   validate_compression(input, compression_options);
-  /* multi-column keys, and any STRING key: placement on the fused key chain
-   * (our spec, dj_hash.h — MurmurHash3 placement is parity-unpinned,
-   * SURVEY.md §8c) */
-  DBuf fused;
-  const bool str_key = any_string_key(input, on_columns);
-  if (on_columns.size() > 1 || str_key) {
-    DJ_CHECK_ERROR(hash_fn != DJ_HASH_IDENTITY || !str_key,
-                   "identity-hash shuffle is not defined for STRING key columns "
-                   "(cuDF has no identity hash for strings either); use HASH_MURMUR3");
-    DJ_CHECK_ERROR(hash_fn != DJ_HASH_IDENTITY,
-                   "identity-hash shuffle requires a single key column");
-    fused = fuse_keys(input, on_columns, dj_rt_stream());
-  }
-  PartitionedTable part = partition_table(input, on_columns[0], comm_group.size(), hash_fn,
-                                          hash_seed, fused.p ? fused.i64() : nullptr);
+  PartitionedTable part = place_rows(input, on_columns, comm_group.size(), hash_fn, hash_seed);
   AllToAllCommunicator atoa(part.tbl->view(), part.offsets, comm_group, communicator,
                             compression_options, false);
   auto out = atoa.allocate_communicated_table();
@@ -2440,6 +2312,33 @@ std::unique_ptr<cudf::table> collect_tables(cudf::table_view table, Communicator
 /* --------------------------- C ABI over the C++ orchestration (for the
  * Python measurement harness; additive — SURVEY.md §8b) ------------------ */
 
+namespace {
+
+/* dj_col_desc[nc] (include/distributed_join.h) -> table view of n rows */
+cudf::table_view view_from_descs(const dj_col_desc* cols, int nc, int64_t n)
+{
+  using cudf::data_type;
+  using cudf::type_id;
+  std::vector<cudf::column_view> v;
+  for (int c = 0; c < nc; c++) {
+    if ((type_id)cols[c].type_id == type_id::STRING)
+      v.emplace_back(data_type(type_id::STRING), (cudf::size_type)n, cols[c].data,
+                     cols[c].chars, cols[c].chars_bytes);
+    else
+      v.emplace_back(data_type((type_id)cols[c].type_id), (cudf::size_type)n, cols[c].data);
+  }
+  return cudf::table_view(v);
+}
+
+/* DJ_HASH_* of the C header -> cudf::hash_id */
+cudf::hash_id to_hash_id(int hash_function)
+{
+  return hash_function == DJ_HASH_IDENTITY ? cudf::hash_id::HASH_IDENTITY
+                                           : cudf::hash_id::HASH_MURMUR3;
+}
+
+}  // namespace
+
 extern "C" {
 
 void* dj_cpp_comm_create(int rank, int size, const void* id_bytes)
@@ -2489,49 +2388,8 @@ int dj_rccl_selftest(int64_t n)
 }
 
 /* full distributed_inner_join over int64 key/payload columns; returns an
- * opaque cudf::table* */
-void* dj_cpp_distributed_inner_join_i64(void* comm, const int64_t* d_lk, const int64_t* d_lp,
-                                        int64_t ln, const int64_t* d_rk, const int64_t* d_rp,
-                                        int64_t rn, int over_decom, int report_timing)
-{
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  cudf::table_view left(
-    {column_view(data_type(type_id::INT64), (cudf::size_type)ln, d_lk),
-     column_view(data_type(type_id::INT64), (cudf::size_type)ln, d_lp)});
-  cudf::table_view right(
-    {column_view(data_type(type_id::INT64), (cudf::size_type)rn, d_rk),
-     column_view(data_type(type_id::INT64), (cudf::size_type)rn, d_rp)});
-  auto opts = generate_compression_options_distributed(left, false);
-  auto result = distributed_inner_join(left, right, {0}, {0}, (Communicator*)comm, opts, opts,
-                                       over_decom, report_timing != 0, nullptr, 1);
-  return result.release();
-}
-
-/* join with compression options (cascaded bitpack when compression != 0) */
-void* dj_cpp_distributed_inner_join_i64_opts(void* comm, const int64_t* d_lk,
-                                             const int64_t* d_lp, int64_t ln,
-                                             const int64_t* d_rk, const int64_t* d_rp,
-                                             int64_t rn, int over_decom, int report_timing,
-                                             int compression)
-{
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  cudf::table_view left(
-    {column_view(data_type(type_id::INT64), (cudf::size_type)ln, d_lk),
-     column_view(data_type(type_id::INT64), (cudf::size_type)ln, d_lp)});
-  cudf::table_view right(
-    {column_view(data_type(type_id::INT64), (cudf::size_type)rn, d_rk),
-     column_view(data_type(type_id::INT64), (cudf::size_type)rn, d_rp)});
-  auto opts = generate_compression_options_distributed(left, compression != 0);
-  auto result = distributed_inner_join(left, right, {0}, {0}, (Communicator*)comm, opts, opts,
-                                       over_decom, report_timing != 0, nullptr, 1);
-  return result.release();
-}
-
-/* full-featured variant: adds nvlink_domain_size. The reference's README
+ * opaque cudf::table*. Cascaded bitpack on the wire when compression != 0;
+ * nvlink_domain_size as in the C++ API. The reference's README
  * benchmark runs with its default nvlink_domain_size=1 (IB-domain shuffle of
  * both tables + local join, distributed_join.cpp:152-199 + README.md:73-86);
  * on one 8x MI355X node the whole node is ONE xGMI domain, so
@@ -2543,15 +2401,7 @@ void* dj_cpp_distributed_inner_join_i64_full(void* comm, const int64_t* d_lk,
                                              int64_t rn, int over_decom, int report_timing,
                                              int compression, int nvlink_domain_size)
 {
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  cudf::table_view left(
-    {column_view(data_type(type_id::INT64), (cudf::size_type)ln, d_lk),
-     column_view(data_type(type_id::INT64), (cudf::size_type)ln, d_lp)});
-  cudf::table_view right(
-    {column_view(data_type(type_id::INT64), (cudf::size_type)rn, d_rk),
-     column_view(data_type(type_id::INT64), (cudf::size_type)rn, d_rp)});
+  cudf::table_view left = view_i64_pair(d_lk, d_lp, ln), right = view_i64_pair(d_rk, d_rp, rn);
   auto opts = generate_compression_options_distributed(left, compression != 0);
   auto result = distributed_inner_join(left, right, {0}, {0}, (Communicator*)comm, opts, opts,
                                        over_decom, report_timing != 0, nullptr,
@@ -2559,40 +2409,40 @@ void* dj_cpp_distributed_inner_join_i64_full(void* comm, const int64_t* d_lk,
   return result.release();
 }
 
+/* the same without compression, nvlink_domain_size = 1 */
+void* dj_cpp_distributed_inner_join_i64(void* comm, const int64_t* d_lk, const int64_t* d_lp,
+                                        int64_t ln, const int64_t* d_rk, const int64_t* d_rp,
+                                        int64_t rn, int over_decom, int report_timing)
+{
+  return dj_cpp_distributed_inner_join_i64_full(comm, d_lk, d_lp, ln, d_rk, d_rp, rn,
+                                                over_decom, report_timing, 0, 1);
+}
+
+/* the same with nvlink_domain_size = 1 */
+void* dj_cpp_distributed_inner_join_i64_opts(void* comm, const int64_t* d_lk,
+                                             const int64_t* d_lp, int64_t ln,
+                                             const int64_t* d_rk, const int64_t* d_rp,
+                                             int64_t rn, int over_decom, int report_timing,
+                                             int compression)
+{
+  return dj_cpp_distributed_inner_join_i64_full(comm, d_lk, d_lp, ln, d_rk, d_rp, rn,
+                                                over_decom, report_timing, compression, 1);
+}
+
 void* dj_cpp_shuffle_on_i64_comp(void* comm, const int64_t* d_keys, const int64_t* d_pay,
                                  int64_t n, int hash_function, uint32_t seed, int compression)
 {
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  cudf::table_view input(
-    {column_view(data_type(type_id::INT64), (cudf::size_type)n, d_keys),
-     column_view(data_type(type_id::INT64), (cudf::size_type)n, d_pay)});
+  cudf::table_view input = view_i64_pair(d_keys, d_pay, n);
   auto opts = generate_compression_options_distributed(input, compression != 0);
-  auto result =
-    shuffle_on(input, {0}, (Communicator*)comm, opts,
-               hash_function == DJ_HASH_IDENTITY ? cudf::hash_id::HASH_IDENTITY
-                                                 : cudf::hash_id::HASH_MURMUR3,
-               seed, false, nullptr);
+  auto result = shuffle_on(input, {0}, (Communicator*)comm, opts, to_hash_id(hash_function),
+                           seed, false, nullptr);
   return result.release();
 }
 
 void* dj_cpp_shuffle_on_i64(void* comm, const int64_t* d_keys, const int64_t* d_pay, int64_t n,
                             int hash_function, uint32_t seed)
 {
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  cudf::table_view input(
-    {column_view(data_type(type_id::INT64), (cudf::size_type)n, d_keys),
-     column_view(data_type(type_id::INT64), (cudf::size_type)n, d_pay)});
-  auto opts = generate_compression_options_distributed(input, false);
-  auto result =
-    shuffle_on(input, {0}, (Communicator*)comm, opts,
-               hash_function == DJ_HASH_IDENTITY ? cudf::hash_id::HASH_IDENTITY
-                                                 : cudf::hash_id::HASH_MURMUR3,
-               seed, false, nullptr);
-  return result.release();
+  return dj_cpp_shuffle_on_i64_comp(comm, d_keys, d_pay, n, hash_function, seed, 0);
 }
 
 /* deterministic test/bench string payload from keys (string_payload.cu
@@ -2647,67 +2497,33 @@ void* dj_cpp_distributed_inner_join_i64str(void* comm, const int64_t* d_lk,
  * int64 key + string payload on one side, int64 key + int64 payload on the
  * other). dj_col_desc: include/distributed_join.h; type_id: 2=INT32,
  * 3=INT64, 4=STRING (cudf::type_id values). Key indices may name STRING
- * columns. */
-
-void* dj_cpp_distributed_inner_join_cols(void* comm, const dj_col_desc* lcols, int nl,
-                                         int64_t ln, const dj_col_desc* rcols, int nr,
-                                         int64_t rn, int key_l, int key_r, int over_decom,
-                                         int report_timing)
-{
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  auto mk = [](const dj_col_desc* cols, int nc, int64_t n) {
-    std::vector<column_view> v;
-    for (int c = 0; c < nc; c++) {
-      if ((type_id)cols[c].type_id == type_id::STRING)
-        v.emplace_back(data_type(type_id::STRING), (cudf::size_type)n, cols[c].data,
-                       cols[c].chars, cols[c].chars_bytes);
-      else
-        v.emplace_back(data_type((type_id)cols[c].type_id), (cudf::size_type)n, cols[c].data);
-    }
-    return cudf::table_view(v);
-  };
-  auto left = mk(lcols, nl, ln);
-  auto right = mk(rcols, nr, rn);
-  auto lopts = generate_compression_options_distributed(left, false);
-  auto ropts = generate_compression_options_distributed(right, false);
-  auto result = distributed_inner_join(left, right, {(cudf::size_type)key_l},
-                                       {(cudf::size_type)key_r}, (Communicator*)comm, lopts,
-                                       ropts, over_decom, report_timing != 0, nullptr, 1);
-  return result.release();
-}
-
-/* multi-column-key variant: lon/ron are int32 arrays of nkeys column
- * indices (distributed_inner_join with composite left_on/right_on) */
+ * columns. lon/ron are int32 arrays of nkeys column indices
+ * (distributed_inner_join with composite left_on/right_on). */
 void* dj_cpp_distributed_inner_join_cols_multi(void* comm, const dj_col_desc* lcols, int nl,
                                                int64_t ln, const dj_col_desc* rcols, int nr,
                                                int64_t rn, const int32_t* lon,
                                                const int32_t* ron, int nkeys, int over_decom,
                                                int report_timing)
 {
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  auto mk = [](const dj_col_desc* cols, int nc, int64_t n) {
-    std::vector<column_view> v;
-    for (int c = 0; c < nc; c++) {
-      if ((type_id)cols[c].type_id == type_id::STRING)
-        v.emplace_back(data_type(type_id::STRING), (cudf::size_type)n, cols[c].data,
-                       cols[c].chars, cols[c].chars_bytes);
-      else
-        v.emplace_back(data_type((type_id)cols[c].type_id), (cudf::size_type)n, cols[c].data);
-    }
-    return cudf::table_view(v);
-  };
-  auto left = mk(lcols, nl, ln);
-  auto right = mk(rcols, nr, rn);
+  auto left = view_from_descs(lcols, nl, ln);
+  auto right = view_from_descs(rcols, nr, rn);
   std::vector<cudf::size_type> lo(lon, lon + nkeys), ro(ron, ron + nkeys);
   auto lopts = generate_compression_options_distributed(left, false);
   auto ropts = generate_compression_options_distributed(right, false);
   auto result = distributed_inner_join(left, right, lo, ro, (Communicator*)comm, lopts,
                                        ropts, over_decom, report_timing != 0, nullptr, 1);
   return result.release();
+}
+
+/* single-key variant */
+void* dj_cpp_distributed_inner_join_cols(void* comm, const dj_col_desc* lcols, int nl,
+                                         int64_t ln, const dj_col_desc* rcols, int nr,
+                                         int64_t rn, int key_l, int key_r, int over_decom,
+                                         int report_timing)
+{
+  const int32_t lon = key_l, ron = key_r;
+  return dj_cpp_distributed_inner_join_cols_multi(comm, lcols, nl, ln, rcols, nr, rn, &lon,
+                                                  &ron, 1, over_decom, report_timing);
 }
 
 /* shuffle_on over column descriptors; `on` names nkeys key columns, STRING
@@ -2721,18 +2537,7 @@ void* dj_cpp_shuffle_on_cols(void* comm, const dj_col_desc* cols, int nc, int64_
                              const int32_t* on, int nkeys, int hash_function, uint32_t seed,
                              int compression)
 {
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  std::vector<column_view> v;
-  for (int c = 0; c < nc; c++) {
-    if ((type_id)cols[c].type_id == type_id::STRING)
-      v.emplace_back(data_type(type_id::STRING), (cudf::size_type)n, cols[c].data,
-                     cols[c].chars, cols[c].chars_bytes);
-    else
-      v.emplace_back(data_type((type_id)cols[c].type_id), (cudf::size_type)n, cols[c].data);
-  }
-  cudf::table_view input(v);
+  cudf::table_view input = view_from_descs(cols, nc, n);
   std::vector<cudf::size_type> keys(on, on + nkeys);
   std::vector<ColumnCompressionOptions> opts;
   if (compression == 2) {
@@ -2745,11 +2550,8 @@ void* dj_cpp_shuffle_on_cols(void* comm, const dj_col_desc* cols, int nc, int64_
     opts = generate_compression_options_distributed(input, compression != 0);
   }
   try {
-    auto result =
-      shuffle_on(input, keys, (Communicator*)comm, opts,
-                 hash_function == DJ_HASH_IDENTITY ? cudf::hash_id::HASH_IDENTITY
-                                                   : cudf::hash_id::HASH_MURMUR3,
-                 seed, false, nullptr);
+    auto result = shuffle_on(input, keys, (Communicator*)comm, opts, to_hash_id(hash_function),
+                             seed, false, nullptr);
     return result.release();
   } catch (std::exception const& e) {
     /* no exception crosses the C ABI: loud exit, as DJ_CHECK_ERROR */
@@ -2758,39 +2560,21 @@ void* dj_cpp_shuffle_on_cols(void* comm, const dj_col_desc* cols, int nc, int64_
   }
 }
 
-/* test hook: the placement step of shuffle_on alone. Partitions the table
- * into nparts contiguous ranges exactly as shuffle_on does before its
- * all-to-all (same key widening / fused chain, same stable partition, same
- * table gather) and writes the nparts+1 row offsets to h_offsets. Lets one
- * GPU check placement against the dj_hash.h spec for nparts > 1. */
+/* test hook: the placement step of shuffle_on alone (place_rows, the very
+ * function shuffle_on calls before its all-to-all). Partitions the table
+ * into nparts contiguous ranges and writes the nparts+1 row offsets to
+ * h_offsets. Lets one GPU check placement against the dj_hash.h spec for
+ * nparts > 1. */
 void* dj_cpp_partition_cols(const dj_col_desc* cols, int nc, int64_t n, const int32_t* on,
                             int nkeys, int nparts, int hash_function, uint32_t seed,
                             int64_t* h_offsets)
 {
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  std::vector<column_view> v;
-  for (int c = 0; c < nc; c++) {
-    if ((type_id)cols[c].type_id == type_id::STRING)
-      v.emplace_back(data_type(type_id::STRING), (cudf::size_type)n, cols[c].data,
-                     cols[c].chars, cols[c].chars_bytes);
-    else
-      v.emplace_back(data_type((type_id)cols[c].type_id), (cudf::size_type)n, cols[c].data);
-  }
-  cudf::table_view input(v);
-  std::vector<cudf::size_type> keys(on, on + nkeys);
   DJ_CHECK_ERROR(nkeys >= 1 && nkeys <= 4, "partition: 1..4 key columns");
   DJ_CHECK_ERROR(nparts >= 1 && nparts <= dj::kMaxPartitions, "partition: 1..1024 parts");
-  const int hash_fn = hash_function == DJ_HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3;
-  DBuf fused;
-  if (nkeys > 1 || any_string_key(input, keys)) {
-    DJ_CHECK_ERROR(hash_fn != DJ_HASH_IDENTITY,
-                   "identity-hash placement requires a single integer key column");
-    fused = fuse_keys(input, keys, dj_rt_stream());
-  }
+  std::vector<cudf::size_type> keys(on, on + nkeys);
   PartitionedTable part =
-    partition_table(input, keys[0], nparts, hash_fn, seed, fused.p ? fused.i64() : nullptr);
+    place_rows(view_from_descs(cols, nc, n), keys, nparts,
+               hash_function == DJ_HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3, seed);
   for (int i = 0; i <= nparts; i++) h_offsets[i] = part.offsets[(size_t)i];
   return part.tbl.release();
 }
@@ -2865,12 +2649,7 @@ void dj_string_keys64(const void* d_offsets, const void* d_chars, int64_t chars_
 void* dj_cpp_distribute_collect_roundtrip_i64(void* comm, const int64_t* d_keys,
                                               const int64_t* d_pay, int64_t n)
 {
-  using cudf::column_view;
-  using cudf::data_type;
-  using cudf::type_id;
-  cudf::table_view global(
-    {column_view(data_type(type_id::INT64), (cudf::size_type)n, d_keys),
-     column_view(data_type(type_id::INT64), (cudf::size_type)n, d_pay)});
+  cudf::table_view global = view_i64_pair(d_keys, d_pay, n);
   auto local = distribute_table(global, (Communicator*)comm);
   auto merged = collect_tables(local->view(), (Communicator*)comm);
   return merged.release();

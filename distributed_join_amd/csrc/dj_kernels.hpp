@@ -196,8 +196,8 @@ void hash_strings(const int32_t* d_offsets, const uint8_t* d_chars, int64_t n, u
 /* same kernel, d_out[i] = dj_murmur3_bytes(row i, seed) (test hook) */
 void hash_strings_seeded(const int32_t* d_offsets, const uint8_t* d_chars, int64_t n,
                          uint32_t seed, uint32_t* d_out, hipStream_t s);
-/* collision filter over key tuples with STRING columns: keep the (li, ri)
- * pairs whose key tuples are equal column by column (strings: length, then
+/* collision filter over key tuples of integer-rep and STRING columns: keep
+ * the (li, ri) pairs whose key tuples are equal column by column (strings: length, then
  * bytes); appends to d_out_li/d_out_ri at positions drawn from *d_count
  * (caller-zeroed), order unspecified. Per column and side: kind, data
  * (values, or int32 offsets for kKeyStr) and chars (kKeyStr only). */

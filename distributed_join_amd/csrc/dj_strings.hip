@@ -530,9 +530,7 @@ void hash_strings_seeded(const int32_t* d_offsets, const uint8_t* d_chars, int64
   launch_hash_strings(d_offsets, d_chars, n, seed, seed, nullptr, d_out, s);
 }
 
-/* ---- collision filter over key tuples that may hold STRING columns ----
- * Sibling of filter_tuple_matches_kernel (dj_cpp_api.hip), which keeps
- * serving integer-only tuples unchanged. */
+/* ---- collision filter over key tuples: integer-rep and STRING columns ---- */
 
 /* lengths first, then bytes; reads exactly [a, a+la) and [b, b+la) and
  * nothing at all for two empty strings */

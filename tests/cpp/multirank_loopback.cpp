@@ -129,14 +129,25 @@ extern "C" void dj_gen_test_strings(const int64_t* d_keys, int64_t n, void** out
                                     void** out_chars, int64_t* out_chars_bytes);
 extern "C" void dj_dfree(void* p);
 
+/* key of global row i under key_mode 1 / 2 (both tables alike): 97 distinct
+ * keys, each many times over on both sides; mode 1 shifts them so that one
+ * of them is the engine's reserved sentinel -1. Mode 3: every key is -1. */
+static int64_t dup_key(int64_t i, int key_mode)
+{
+  return key_mode == 3 ? -1 : i % 97 - (key_mode == 1 ? 1 : 0);
+}
+
 static std::unique_ptr<cudf::table> make_rank_tables(int64_t n_global, int64_t rows,
-                                                     int64_t row0, bool build)
+                                                     int64_t row0, bool build, int key_mode = 0)
 {
   std::vector<int64_t> keys(rows), pay(rows);
   for (int64_t t = 0; t < rows; t++) {
     int64_t i = row0 + t;
-    keys[t] = build ? dj_build_key((uint64_t)i, (uint64_t)n_global, 2 * n_global, 1234)
-                    : dj_probe_key((uint64_t)i, (uint64_t)n_global, 2 * n_global, 0.3, 1234);
+    if (key_mode != 0)
+      keys[t] = dup_key(i, key_mode);
+    else
+      keys[t] = build ? dj_build_key((uint64_t)i, (uint64_t)n_global, 2 * n_global, 1234)
+                      : dj_probe_key((uint64_t)i, (uint64_t)n_global, 2 * n_global, 0.3, 1234);
     pay[t] = i;
   }
   auto kcol = std::make_unique<cudf::column>(cudf::data_type(cudf::type_id::INT64),
@@ -251,14 +262,29 @@ int main(int argc, char** argv)
   const int G = argc > 1 ? atoi(argv[1]) : 2;
   const int over_decom = argc > 2 ? atoi(argv[2]) : 2;
   const int64_t n_global = argc > 3 ? atoll(argv[3]) : 400000;
+  /* argv[4] nvlink_domain_size, argv[5] compression (read where used);
+   * argv[6] is reserved (pass 0); argv[7] key_mode of the main join:
+   *   0  generator keys (unique build keys, never -1);
+   *   2  key = i % 97 on both sides: every key matches many times over, the
+   *      batch's match count exceeds its first-try capacity;
+   *   1  key = i % 97 - 1: the same, and key -1 sets the sentinel flag;
+   *   3  key = -1 everywhere: the enqueued join skips every row, so its
+   *      count is 0 with the sentinel flag set, and all n_global^2 rows
+   *      come from the redo.
+   * Modes 1 to 3 drive batch finalisation into its redo branch (the batch
+   * is re-joined synchronously). The tables stay 2 x INT64 with the key at
+   * column 0, so with nvlink_domain_size = G and G * over_decom <= 256 —
+   * which is what leaves distributed_inner_join's `pa >= 4` — the batches
+   * run on the fused wire path. */
+  const int key_mode = argc > 7 ? atoi(argv[7]) : 0;
   CHECK(hipSetDevice(0));
 
   /* reference: single-rank result on the concatenated inputs */
   uint64_t want_sum;
   int64_t want_rows;
   {
-    auto left = make_rank_tables(n_global, n_global, 0, true);
-    auto right = make_rank_tables(n_global, n_global, 0, false);
+    auto left = make_rank_tables(n_global, n_global, 0, true, key_mode);
+    auto right = make_rank_tables(n_global, n_global, 0, false, key_mode);
     Mailbox mb;
     LoopbackCommunicator comm(0, 1, &mb);
     auto opts = generate_compression_options_distributed(left->view(), false);
@@ -276,8 +302,8 @@ int main(int argc, char** argv)
     threads.emplace_back([&, r] {
       CHECK(hipSetDevice(0));
       int64_t per = n_global / G;
-      auto left = make_rank_tables(n_global, per, r * per, true);
-      auto right = make_rank_tables(n_global, per, r * per, false);
+      auto left = make_rank_tables(n_global, per, r * per, true, key_mode);
+      auto right = make_rank_tables(n_global, per, r * per, false, key_mode);
       LoopbackCommunicator comm(r, G, &mb);
       /* alternate per-rank-invariant variants across runs of this binary via
        * argv: nvlink_domain_size and compression are exercised by the python
@@ -512,6 +538,18 @@ int main(int argc, char** argv)
   if (got_rows != want_rows || got_sum != want_sum) {
     printf("MULTIRANK MISMATCH\n");
     return 1;
+  }
+  if (key_mode != 0) {
+    /* closed form: sum over keys of (left count x right count) */
+    std::map<int64_t, int64_t> count;
+    for (int64_t i = 0; i < n_global; i++) count[dup_key(i, key_mode)]++;
+    int64_t closed = 0;
+    for (auto& kv : count) closed += kv.second * kv.second;
+    printf("closed form: rows=%lld\n", (long long)closed);
+    if (got_rows != closed) {
+      printf("MULTIRANK ROW COUNT MISMATCH\n");
+      return 1;
+    }
   }
   printf("MULTIRANK OK\n");
   return 0;

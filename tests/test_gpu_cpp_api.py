@@ -124,8 +124,17 @@ def test_multirank_loopback():
              "-o", exe, "-L", os.path.join(repo, "distributed_join_amd"), "-ldistjoin",
              "-Wl,-rpath," + os.path.join(repo, "distributed_join_amd")],
             check=True, capture_output=True)
-    # (G, over_decom, n_global, nvlink_domain_size, compression)
-    for args in (["2", "2"], ["4", "1"],
+    # (G, over_decom, n_global, nvlink_domain_size, compression, reserved,
+    #  key_mode); key_mode 1/2: heavily duplicated keys (1: one of them -1),
+    # 3880 = 97 x 40 rows -> 97 x 40 x 40 = 155200 joined rows; key_mode 3:
+    # every key -1 -> 776 x 776 rows. Every non-empty batch of the fused wire
+    # path is finalised through its redo branch.
+    closed_form = {"1": 155200, "2": 155200, "3": 776 * 776}
+    for args in (["2", "2", "3880", "2", "0", "0", "1"],
+                 ["4", "1", "3880", "4", "0", "0", "1"],
+                 ["2", "2", "3880", "2", "0", "0", "2"],
+                 ["2", "2", "776", "2", "0", "0", "3"],
+                 ["2", "2"], ["4", "1"],
                  ["4", "1", "400000", "2", "0"],   # 2-level hierarchy
                  ["4", "1", "400000", "1", "0"],   # nvl=1: full shuffle + local join
                  ["2", "2", "400000", "2", "1"],   # compressed wire
@@ -135,6 +144,8 @@ def test_multirank_loopback():
         r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=240)
         assert r.returncode == 0, " ".join(args) + "\n" + r.stdout + r.stderr
         assert "MULTIRANK OK" in r.stdout
+        if len(args) > 6:
+            assert "closed form: rows=%d\n" % closed_form[args[6]] in r.stdout, r.stdout
 
 
 def test_rccl_selftest(dj):

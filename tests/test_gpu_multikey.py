@@ -2,7 +2,7 @@
 
 The engine joins on a fused hash chain of the key tuple and filters
 fused-hash collisions against the real columns (dj_cpp_api.hip
-local_inner_join_multi) — reference semantics: cudf::inner_join on
+local_inner_join) — reference semantics: cudf::inner_join on
 arbitrary left_on/right_on (distributed_join.cpp:71-132). Parity oracle:
 the single-key CPU join on a collision-free combined key
 (k0 * 2^32 + k1, exact in int64 for the test ranges).
@@ -104,7 +104,7 @@ def test_int64_plus_int32_keys(dj, comm):
 def test_collision_filter_under_weak_fuse():
     """DJ_TEST_WEAK_FUSE collapses the fused hash to 4 bits, so nearly every
     bucket match is a hash collision — the result must still be exact
-    (pins filter_tuple_matches_kernel, which real fused hashes almost never
+    (pins filter_tuple_matches_mixed_kernel, which real fused hashes almost never
     exercise). Runs in a subprocess: the env is read once per process."""
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = r"""
