@@ -261,7 +261,7 @@ int64_t dj_local_inner_join(const int64_t* d_lk, const int64_t* d_lp, int64_t ln
 namespace {
 
 /* round-2 local join uses the count-free slack bucket layout (pass B writes
- * bucket b at b*capB with length lens[b] — bucket_partition2_slack) whenever
+ * bucket b at b*capB with length lens[b] — bucket_partition2_slack_pair) whenever
  * its u32 row indices fit; otherwise the exact compact path. */
 bool bucket_slack_mode(int64_t ln, int64_t rn, int B)
 {

@@ -49,6 +49,13 @@ __device__ __forceinline__ longlong2 nt_load2(const longlong2* p)
   return v;
 }
 
+/* every kernel launch in this file: the launch and its error check */
+#define DJ_LAUNCH(kern, grid, block, lds, s, ...)               \
+  do {                                                          \
+    hipLaunchKernelGGL(kern, grid, block, lds, s, __VA_ARGS__); \
+    DJ_HIP_CALL(hipGetLastError());                             \
+  } while (0)
+
 /* ------------------------------------------------------------------ misc */
 
 __global__ void fill_i64_kernel(int64_t* dst, int64_t value, int64_t n)
@@ -116,11 +123,10 @@ void neg1_cross_join(const int64_t* d_lk, const int64_t* d_lp, int64_t ln,
   DJ_HIP_CALL(hipMalloc(&d_cnt, 16));
   DJ_HIP_CALL(hipMemsetAsync(d_cnt, 0, 16, s));
   /* pass 1: count (cap 0 => no payload writes) */
-  hipLaunchKernelGGL(collect_neg1_kernel, dim3(grid_for(ln)), dim3(BLOCK), 0, s, d_lk, d_lp,
-                     ln, nullptr, d_cnt, 0);
-  hipLaunchKernelGGL(collect_neg1_kernel, dim3(grid_for(rn)), dim3(BLOCK), 0, s, d_rk, d_rp,
-                     rn, nullptr, d_cnt + 1, 0);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(collect_neg1_kernel, dim3(grid_for(ln)), dim3(BLOCK), 0, s, d_lk, d_lp, ln, nullptr,
+            d_cnt, 0);
+  DJ_LAUNCH(collect_neg1_kernel, dim3(grid_for(rn)), dim3(BLOCK), 0, s, d_rk, d_rp, rn, nullptr,
+            d_cnt + 1, 0);
   unsigned long long h_cnt[2] = {0, 0};
   DJ_HIP_CALL(hipMemcpyAsync(h_cnt, d_cnt, 16, hipMemcpyDeviceToHost, s));
   DJ_HIP_CALL(hipStreamSynchronize(s));
@@ -130,11 +136,10 @@ void neg1_cross_join(const int64_t* d_lk, const int64_t* d_lp, int64_t ln,
     DJ_HIP_CALL(hipMalloc(&d_lpv, (size_t)n1 * 8));
     DJ_HIP_CALL(hipMalloc(&d_rpv, (size_t)n2 * 8));
     DJ_HIP_CALL(hipMemsetAsync(d_cnt, 0, 16, s));
-    hipLaunchKernelGGL(collect_neg1_kernel, dim3(grid_for(ln)), dim3(BLOCK), 0, s, d_lk,
-                       d_lp, ln, d_lpv, d_cnt, n1);
-    hipLaunchKernelGGL(collect_neg1_kernel, dim3(grid_for(rn)), dim3(BLOCK), 0, s, d_rk,
-                       d_rp, rn, d_rpv, d_cnt + 1, n2);
-    DJ_HIP_CALL(hipGetLastError());
+    DJ_LAUNCH(collect_neg1_kernel, dim3(grid_for(ln)), dim3(BLOCK), 0, s, d_lk, d_lp, ln,
+              d_lpv, d_cnt, n1);
+    DJ_LAUNCH(collect_neg1_kernel, dim3(grid_for(rn)), dim3(BLOCK), 0, s, d_rk, d_rp, rn,
+              d_rpv, d_cnt + 1, n2);
     int64_t base = 0;
     DJ_HIP_CALL(hipMemcpyAsync(&base, d_counter, 8, hipMemcpyDeviceToHost, s));
     DJ_HIP_CALL(hipStreamSynchronize(s));
@@ -142,9 +147,8 @@ void neg1_cross_join(const int64_t* d_lk, const int64_t* d_lp, int64_t ln,
     DJ_CHECK_ERROR(n1 <= INT64_MAX / n2,
                    "join: cross product of the -1 keys overflows int64 rows");
     const int64_t total = n1 * n2;
-    hipLaunchKernelGGL(emit_neg1_cross_kernel, dim3(grid_for(total)), dim3(BLOCK), 0, s,
-                       d_lpv, n1, d_rpv, n2, base, d_out0, d_out1, d_out2, d_out3, cap);
-    DJ_HIP_CALL(hipGetLastError());
+    DJ_LAUNCH(emit_neg1_cross_kernel, dim3(grid_for(total)), dim3(BLOCK), 0, s, d_lpv, n1,
+              d_rpv, n2, base, d_out0, d_out1, d_out2, d_out3, cap);
     const int64_t newcount = base + total;
     DJ_HIP_CALL(hipMemcpyAsync(d_counter, &newcount, 8, hipMemcpyHostToDevice, s));
     DJ_HIP_CALL(hipStreamSynchronize(s));
@@ -157,8 +161,7 @@ void neg1_cross_join(const int64_t* d_lk, const int64_t* d_lp, int64_t ln,
 void fill_i64(int64_t* d_dst, int64_t value, int64_t n, hipStream_t s)
 {
   if (n <= 0) return;
-  hipLaunchKernelGGL(fill_i64_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, s, d_dst, value, n);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(fill_i64_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, s, d_dst, value, n);
 }
 
 /* ----------------------------------------------------------- table gather
@@ -277,9 +280,8 @@ static void launch_gather_fused(const GatherDesc& d, const int64_t* d_idx, int64
                                 hipStream_t s)
 {
   const int64_t nthreads = std::max<int64_t>(n >> 2, 4);
-  hipLaunchKernelGGL(gather_table_kernel, dim3(grid_for(nthreads)), dim3(BLOCK), 0, s, d,
-                     d_idx, n, ((uintptr_t)d_idx & 15) == 0 ? 1 : 0);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(gather_table_kernel, dim3(grid_for(nthreads)), dim3(BLOCK), 0, s, d, d_idx, n,
+            ((uintptr_t)d_idx & 15) == 0 ? 1 : 0);
 }
 
 void gather_table(const GatherCol* cols, int ncols, const int64_t* d_idx, int64_t n, int mode,
@@ -311,23 +313,22 @@ void gather_table(const GatherCol* cols, int ncols, const int64_t* d_idx, int64_
     }
     switch (col.width) {
       case 1:
-        hipLaunchKernelGGL((gather_col_kernel<uint8_t>), dim3(grid_for(n)), dim3(BLOCK), 0, s,
-                           (const uint8_t*)col.src, d_idx, n, (uint8_t*)col.dst);
+        DJ_LAUNCH(gather_col_kernel<uint8_t>, dim3(grid_for(n)), dim3(BLOCK), 0, s,
+                  (const uint8_t*)col.src, d_idx, n, (uint8_t*)col.dst);
         break;
       case 2:
-        hipLaunchKernelGGL((gather_col_kernel<uint16_t>), dim3(grid_for(n)), dim3(BLOCK), 0, s,
-                           (const uint16_t*)col.src, d_idx, n, (uint16_t*)col.dst);
+        DJ_LAUNCH(gather_col_kernel<uint16_t>, dim3(grid_for(n)), dim3(BLOCK), 0, s,
+                  (const uint16_t*)col.src, d_idx, n, (uint16_t*)col.dst);
         break;
       case 4:
-        hipLaunchKernelGGL((gather_col_kernel<uint32_t>), dim3(grid_for(n)), dim3(BLOCK), 0, s,
-                           (const uint32_t*)col.src, d_idx, n, (uint32_t*)col.dst);
+        DJ_LAUNCH(gather_col_kernel<uint32_t>, dim3(grid_for(n)), dim3(BLOCK), 0, s,
+                  (const uint32_t*)col.src, d_idx, n, (uint32_t*)col.dst);
         break;
       default:
-        hipLaunchKernelGGL((gather_col_kernel<uint64_t>), dim3(grid_for(n)), dim3(BLOCK), 0, s,
-                           (const uint64_t*)col.src, d_idx, n, (uint64_t*)col.dst);
+        DJ_LAUNCH(gather_col_kernel<uint64_t>, dim3(grid_for(n)), dim3(BLOCK), 0, s,
+                  (const uint64_t*)col.src, d_idx, n, (uint64_t*)col.dst);
         break;
     }
-    DJ_HIP_CALL(hipGetLastError());
   }
   if (d.ncols > 0) launch_gather_fused(d, d_idx, n, s);
 }
@@ -365,18 +366,16 @@ void generate_build(int64_t* d_keys, int64_t* d_pay, int64_t n_global, int64_t r
                     uint64_t seed, bool uniq, int64_t row0, int64_t nrows, hipStream_t s)
 {
   if (nrows <= 0) return;
-  hipLaunchKernelGGL(gen_build_kernel, dim3(grid_for(nrows)), dim3(BLOCK), 0, s, d_keys, d_pay,
-                     n_global, rand_max, seed, (int)uniq, row0, nrows);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(gen_build_kernel, dim3(grid_for(nrows)), dim3(BLOCK), 0, s, d_keys, d_pay, n_global,
+            rand_max, seed, (int)uniq, row0, nrows);
 }
 
 void generate_probe(int64_t* d_keys, int64_t* d_pay, int64_t build_n_global, int64_t rand_max,
                     double selectivity, uint64_t seed, int64_t row0, int64_t nrows, hipStream_t s)
 {
   if (nrows <= 0) return;
-  hipLaunchKernelGGL(gen_probe_kernel, dim3(grid_for(nrows)), dim3(BLOCK), 0, s, d_keys, d_pay,
-                     build_n_global, rand_max, selectivity, seed, row0, nrows);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(gen_probe_kernel, dim3(grid_for(nrows)), dim3(BLOCK), 0, s, d_keys, d_pay,
+            build_n_global, rand_max, selectivity, seed, row0, nrows);
 }
 
 /* ------------------------------------------------------- stable partition */
@@ -575,8 +574,8 @@ void partition_count(const int64_t* d_keys, int64_t n, int nparts, int hash_fn,
   if (n <= 0) return;
   PartGeom g = part_geom(n);
   auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(BLOCK), 0, s, d_keys, n, nparts, hash_fn,
-                       hash_seed, g.rows_per_wave, (int64_t*)d_scratch);
+    DJ_LAUNCH(kern, dim3(g.blocks), dim3(BLOCK), 0, s, d_keys, n, nparts, hash_fn, hash_seed,
+              g.rows_per_wave, (int64_t*)d_scratch);
   };
   if (nparts <= 64)
     launch(part_count_kernel<1>);
@@ -588,7 +587,6 @@ void partition_count(const int64_t* d_keys, int64_t n, int nparts, int hash_fn,
     launch(part_count_kernel<8>);
   else
     launch(part_count_kernel<16>);
-  DJ_HIP_CALL(hipGetLastError());
 }
 
 void partition_scan(int64_t n, int nparts, void* d_scratch, int64_t* d_offsets, hipStream_t s)
@@ -600,11 +598,9 @@ void partition_scan(int64_t n, int nparts, void* d_scratch, int64_t* d_offsets, 
   PartGeom g = part_geom(n);
   int64_t* wave_counts = (int64_t*)d_scratch;
   int64_t* totals = wave_counts + g.nwaves * nparts;
-  hipLaunchKernelGGL(part_scan_kernel, dim3(nparts), dim3(BLOCK), 0, s, wave_counts, g.nwaves,
-                     nparts, totals);
-  DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(part_offsets_kernel, dim3(1), dim3(64), 0, s, totals, nparts, d_offsets);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(part_scan_kernel, dim3(nparts), dim3(BLOCK), 0, s, wave_counts, g.nwaves, nparts,
+            totals);
+  DJ_LAUNCH(part_offsets_kernel, dim3(1), dim3(64), 0, s, totals, nparts, d_offsets);
 }
 
 void partition_scatter(const int64_t* d_keys, const int64_t* d_pay, int64_t n, int nparts,
@@ -614,9 +610,8 @@ void partition_scatter(const int64_t* d_keys, const int64_t* d_pay, int64_t n, i
   if (n <= 0) return;
   PartGeom g = part_geom(n);
   auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(BLOCK), 0, s, d_keys, d_pay, n, nparts,
-                       hash_fn, hash_seed, g.rows_per_wave, (int64_t*)d_scratch, d_offsets,
-                       d_out_keys, d_out_pay);
+    DJ_LAUNCH(kern, dim3(g.blocks), dim3(BLOCK), 0, s, d_keys, d_pay, n, nparts, hash_fn,
+              hash_seed, g.rows_per_wave, (int64_t*)d_scratch, d_offsets, d_out_keys, d_out_pay);
   };
   if (nparts <= 64)
     launch(part_scatter_kernel<1>);
@@ -628,7 +623,6 @@ void partition_scatter(const int64_t* d_keys, const int64_t* d_pay, int64_t n, i
     launch(part_scatter_kernel<8>);
   else
     launch(part_scatter_kernel<16>);
-  DJ_HIP_CALL(hipGetLastError());
 }
 
 void hash_partition(const int64_t* d_keys, const int64_t* d_pay, int64_t n, int nparts,
@@ -690,20 +684,17 @@ void join_build(const int64_t* d_lk, const int64_t* d_lp, int64_t ln, int64_t* d
                 int64_t nslots, int* d_error, hipStream_t s)
 {
   if (ln <= 0) return;
-  hipLaunchKernelGGL(join_build_kernel<false>, dim3(grid_for(ln)), dim3(BLOCK), 0, s, d_lk,
-                     d_lp, (const longlong2*)nullptr, ln, (longlong2*)d_table,
-                     (uint64_t)(nslots - 1), d_error);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(join_build_kernel<false>, dim3(grid_for(ln)), dim3(BLOCK), 0, s, d_lk, d_lp,
+            (const longlong2*)nullptr, ln, (longlong2*)d_table, (uint64_t)(nslots - 1), d_error);
 }
 
 void join_build_pairs(const longlong2* d_rows, int64_t ln, int64_t* d_table, int64_t nslots,
                       int* d_error, hipStream_t s)
 {
   if (ln <= 0) return;
-  hipLaunchKernelGGL(join_build_kernel<true>, dim3(grid_for(ln)), dim3(BLOCK), 0, s,
-                     (const int64_t*)nullptr, (const int64_t*)nullptr, d_rows, ln,
-                     (longlong2*)d_table, (uint64_t)(nslots - 1), d_error);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(join_build_kernel<true>, dim3(grid_for(ln)), dim3(BLOCK), 0, s,
+            (const int64_t*)nullptr, (const int64_t*)nullptr, d_rows, ln, (longlong2*)d_table,
+            (uint64_t)(nslots - 1), d_error);
 }
 
 /* Probe with wave-aggregated output append: matches are emitted via one
@@ -779,11 +770,9 @@ void join_probe(const int64_t* d_rk, const int64_t* d_rp, int64_t rn, const int6
                 int64_t* d_out3, int64_t cap, int64_t* d_counter, hipStream_t s)
 {
   if (rn <= 0) return;
-  hipLaunchKernelGGL(join_probe_kernel<false>, dim3(grid_for(rn)), dim3(BLOCK), 0, s, d_rk,
-                     d_rp, (const longlong2*)nullptr, rn, (const longlong2*)d_table,
-                     (uint64_t)(nslots - 1), d_out0, d_out1, d_out2, d_out3, cap,
-                     (unsigned long long*)d_counter);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(join_probe_kernel<false>, dim3(grid_for(rn)), dim3(BLOCK), 0, s, d_rk, d_rp,
+            (const longlong2*)nullptr, rn, (const longlong2*)d_table, (uint64_t)(nslots - 1),
+            d_out0, d_out1, d_out2, d_out3, cap, (unsigned long long*)d_counter);
 }
 
 void join_probe_pairs(const longlong2* d_rows, int64_t rn, const int64_t* d_table,
@@ -791,11 +780,10 @@ void join_probe_pairs(const longlong2* d_rows, int64_t rn, const int64_t* d_tabl
                       int64_t* d_out3, int64_t cap, int64_t* d_counter, hipStream_t s)
 {
   if (rn <= 0) return;
-  hipLaunchKernelGGL(join_probe_kernel<true>, dim3(grid_for(rn)), dim3(BLOCK), 0, s,
-                     (const int64_t*)nullptr, (const int64_t*)nullptr, d_rows, rn,
-                     (const longlong2*)d_table, (uint64_t)(nslots - 1), d_out0, d_out1,
-                     d_out2, d_out3, cap, (unsigned long long*)d_counter);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(join_probe_kernel<true>, dim3(grid_for(rn)), dim3(BLOCK), 0, s,
+            (const int64_t*)nullptr, (const int64_t*)nullptr, d_rows, rn,
+            (const longlong2*)d_table, (uint64_t)(nslots - 1), d_out0, d_out1, d_out2, d_out3,
+            cap, (unsigned long long*)d_counter);
 }
 
 /* ----------------------------------------------- bucketed LDS join ------ */
@@ -873,7 +861,69 @@ __device__ __forceinline__ uint32_t subF_of(int64_t key, int F)
   return lo | (hi << 8);
 }
 
+/* Compile-time policies of the staged scatters below (staged span, pass-A
+ * chunk scatter, pass-B prologue).
+ * Placement: key -> destination group of one scatter level, fanout() groups.
+ * Rows: the input, two columns or interleaved pairs, read once (nt loads).
+ * Sink: where a staged row goes, pairs or two columns.
+ * The shared bodies take the block size as `nthreads`, which each kernel
+ * passes as its own blockDim.x: read inside a kernel the compiler folds it to
+ * one load (uniform work-groups), read inside a __device__ function it keeps
+ * the partial-last-group form, which cost these kernels 4 to 8 VGPRs. */
+struct PlaceGroupA {  // pass A: groupA_of over P groups
+  int P;
+  __device__ __forceinline__ int fanout() const { return P; }
+  __device__ __forceinline__ uint32_t operator()(int64_t key) const
+  {
+    return groupA_of(key, P);
+  }
+};
+struct PlaceSubF {  // pass B: subF_of over F sub-buckets
+  int F;
+  __device__ __forceinline__ int fanout() const { return F; }
+  __device__ __forceinline__ uint32_t operator()(int64_t key) const { return subF_of(key, F); }
+};
+
+struct ColumnRows {
+  const int64_t* keys;
+  const int64_t* pay;  // nullptr: payload = row index
+  __device__ __forceinline__ int64_t key(int64_t i) const { return nt_load(&keys[i]); }
+  __device__ __forceinline__ longlong2 row(int64_t i) const
+  {
+    longlong2 r;
+    r.x = nt_load(&keys[i]);
+    r.y = pay ? nt_load(&pay[i]) : i;
+    return r;
+  }
+};
+struct PairRows {
+  const longlong2* pairs;
+  __device__ __forceinline__ int64_t key(int64_t i) const { return nt_load(&pairs[i].x); }
+  __device__ __forceinline__ longlong2 row(int64_t i) const { return nt_load2(&pairs[i]); }
+};
+
+struct PairSink {
+  longlong2* out;
+  __device__ __forceinline__ void put(uint32_t dst, longlong2 row) const { out[dst] = row; }
+};
+struct ColumnSink {
+  int64_t* keys;
+  int64_t* pay;
+  __device__ __forceinline__ void put(uint32_t dst, longlong2 row) const
+  {
+    keys[dst] = row.x;
+    pay[dst] = row.y;
+  }
+};
+
 /* ---- pass A kernels (P groups, P <= 1024) ---- */
+
+/* block-chunked count: block b histograms its chunk of the rows in LDS
+ * (u32[P], count_lds_bytes) and writes row b of counts[gridDim][P].
+ * fused_count_kernel below is the same kernel over fused_pid; the two stay
+ * written out — a shared body measured 0.05-0.1% slower on fused_count_kernel
+ * (DESIGN.md §3). */
+static size_t count_lds_bytes(int P) { return (size_t)P * sizeof(uint32_t); }
 
 __global__ __launch_bounds__(BUCKET_THREADS) void bucket_count_kernel(
   const int64_t* __restrict__ keys, int64_t n, int P, uint32_t* __restrict__ counts)
@@ -946,32 +996,41 @@ __global__ void bucket_scanB_kernel(const uint32_t* totals, int P, int64_t* sego
  * (= BUCKET_THREADS: one group per thread in the hist scan). */
 constexpr int SCATTER_TILE = 4096;  // 64 KiB of staged pairs
 
-template <bool SINGLE_LEVEL>
-__device__ __forceinline__ longlong2 load_row(const int64_t* keys, const int64_t* pay,
-                                              const longlong2* pairs, int64_t i)
+/* LDS of the staged kernels: the tile buffer, then `tables` u32[P] tables —
+ * hist, base, gcur for pass A, plus seghist for pass B. staged_lds_bytes is
+ * what the launchers request, staged_lds_carve what the kernels use. */
+constexpr int kPassATables = 3, kPassBTables = 4;
+struct StagedLds {
+  longlong2* tbuf;
+  uint32_t *hist, *base, *gcur, *seghist;
+};
+static size_t staged_lds_bytes(int P, int tables)
 {
-  longlong2 r;
-  if (SINGLE_LEVEL) {
-    r.x = nt_load(&keys[i]);
-    r.y = pay ? nt_load(&pay[i]) : i;
-  } else {
-    r = nt_load2(&pairs[i]);
-  }
-  return r;
+  return SCATTER_TILE * sizeof(longlong2) + (size_t)tables * P * sizeof(uint32_t);
+}
+__device__ __forceinline__ StagedLds staged_lds_carve(int P)
+{
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  StagedLds l;
+  l.tbuf = (longlong2*)smem;
+  l.hist = (uint32_t*)(l.tbuf + SCATTER_TILE);
+  l.base = l.hist + P;
+  l.gcur = l.base + P;
+  l.seghist = l.gcur + P;  // pass B only
+  return l;
 }
 
-/* staged scatter over [start, end); cur[P] holds GLOBAL destination
- * cursors; GROUP_FN: 0 = groupA_of(P), 1 = subF_of(P) */
-template <int GROUP_FN, bool SINGLE_LEVEL>
-__device__ void staged_scatter_span(const int64_t* keys, const int64_t* pay,
-                                    const longlong2* in_pairs, int64_t start, int64_t end,
-                                    int P, longlong2* tbuf, uint32_t* hist, uint32_t* base,
-                                    uint32_t* gcur, longlong2* out_pairs)
-/* GROUP_FN 0: groupA_of(P); GROUP_FN 1: subF_of(P) (P is the runtime
- * fanout; bit fields disjoint from groupA's, see subF_of) */
+/* staged scatter of rows [start, end) of `in`; l.gcur[fanout] holds GLOBAL
+ * destination cursors and is advanced past the span */
+template <class Rows, class Place, class Sink>
+__device__ void staged_scatter_span(Rows in, int64_t start, int64_t end, Place place,
+                                    const StagedLds& l, Sink out, const unsigned nthreads)
 {
   constexpr int VPT = SCATTER_TILE / BUCKET_THREADS;  // 4
   const int tid = threadIdx.x;
+  const int P = place.fanout();
+  longlong2* tbuf = l.tbuf;
+  uint32_t *hist = l.hist, *base = l.base, *gcur = l.gcur;
   for (int64_t t0 = start; t0 < end; t0 += SCATTER_TILE) {
     const int count = (int)min((int64_t)SCATTER_TILE, end - t0);
     if (tid < P) hist[tid] = 0;
@@ -983,10 +1042,10 @@ __device__ void staged_scatter_span(const int64_t* keys, const int64_t* pay,
     uint32_t g[VPT], rank[VPT];
 #pragma unroll
     for (int v = 0; v < VPT; v++) {
-      int64_t i = t0 + (int64_t)v * blockDim.x + tid;
+      int64_t i = t0 + (int64_t)v * nthreads + tid;
       if (i < end) {
-        r[v] = load_row<SINGLE_LEVEL>(keys, pay, in_pairs, i);
-        g[v] = GROUP_FN == 0 ? groupA_of(r[v].x, P) : subF_of(r[v].x, P);
+        r[v] = in.row(i);
+        g[v] = place(r[v].x);
         rank[v] = atomicAdd(&hist[g[v]], 1u);
       }
     }
@@ -1004,15 +1063,15 @@ __device__ void staged_scatter_span(const int64_t* keys, const int64_t* pay,
     __syncthreads();
 #pragma unroll
     for (int v = 0; v < VPT; v++) {
-      int64_t i = t0 + (int64_t)v * blockDim.x + tid;
+      int64_t i = t0 + (int64_t)v * nthreads + tid;
       if (i < end) tbuf[base[g[v]] + rank[v]] = r[v];
     }
     __syncthreads();
     /* flush linearly: per-group runs coalesce into full lines */
-    for (int pos = tid; pos < count; pos += blockDim.x) {
+    for (int pos = tid; pos < count; pos += nthreads) {
       longlong2 row = tbuf[pos];
-      uint32_t gg = GROUP_FN == 0 ? groupA_of(row.x, P) : subF_of(row.x, P);
-      out_pairs[gcur[gg] + (pos - base[gg])] = row;
+      uint32_t gg = place(row.x);
+      out.put(gcur[gg] + (uint32_t)(pos - base[gg]), row);
     }
     __syncthreads();
     if (tid < P) gcur[tid] += hist[tid];
@@ -1020,25 +1079,33 @@ __device__ void staged_scatter_span(const int64_t* keys, const int64_t* pay,
   }
 }
 
+/* counted pass-A scatter: block b seeds its cursors from the group offsets
+ * plus row b of the scanned counts[gridDim][fanout] (the count kernels'
+ * chunking), then scatters its chunk */
+template <class Place, class Sink>
+__device__ __forceinline__ void chunk_scatter(const int64_t* keys, const int64_t* pay,
+                                              int64_t n, Place place, const uint32_t* counts,
+                                              const int64_t* offsets, Sink out,
+                                              const unsigned nthreads)
+{
+  const int P = place.fanout();
+  const StagedLds l = staged_lds_carve(P);
+  if (threadIdx.x < P)
+    l.gcur[threadIdx.x] =
+      (uint32_t)offsets[threadIdx.x] + counts[(size_t)blockIdx.x * P + threadIdx.x];
+  __syncthreads();
+  const int64_t chunk = (n + gridDim.x - 1) / gridDim.x;
+  const int64_t start = (int64_t)blockIdx.x * chunk;
+  const int64_t end = min(start + chunk, n);
+  staged_scatter_span(ColumnRows{keys, pay}, start, end, place, l, out, nthreads);
+}
+
 __global__ __launch_bounds__(BUCKET_THREADS) void bucket_scatter_kernel(
   const int64_t* __restrict__ keys, const int64_t* __restrict__ pay, int64_t n, int P,
   const uint32_t* __restrict__ counts, const int64_t* __restrict__ segoff,
   longlong2* __restrict__ out_pairs)
 {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  longlong2* tbuf = (longlong2*)smem;
-  uint32_t* hist = (uint32_t*)(tbuf + SCATTER_TILE);
-  uint32_t* base = hist + P;
-  uint32_t* gcur = base + P;
-  if (threadIdx.x < P)
-    gcur[threadIdx.x] = (uint32_t)segoff[threadIdx.x] +
-                        counts[(size_t)blockIdx.x * P + threadIdx.x];
-  __syncthreads();
-  const int64_t chunk = (n + gridDim.x - 1) / gridDim.x;
-  const int64_t start = (int64_t)blockIdx.x * chunk;
-  const int64_t end = min(start + chunk, n);
-  staged_scatter_span<0, true>(keys, pay, nullptr, start, end, P, tbuf, hist, base, gcur,
-                               out_pairs);
+  chunk_scatter(keys, pay, n, PlaceGroupA{P}, counts, segoff, PairSink{out_pairs}, blockDim.x);
 }
 
 /* trivial segoff = {0, n} for the single-group (B == 256) case */
@@ -1049,91 +1116,116 @@ __global__ void set_segoff1_kernel(int64_t* segoff, int64_t n)
 }
 
 /* ---- pass B: one block per pass-A group; F sub-buckets in-block ---- */
-/* pass B: one block per pass-A group; F sub-buckets (runtime 256/512/1024,
- * subF_of bit fields disjoint from the pass-A group bits), tile-staged
- * scatter. single_level: input is the original two column arrays (the
- * B == 256 single-pass case). */
-template <bool SINGLE_LEVEL>
-__global__ __launch_bounds__(BUCKET_THREADS) void bucket_subpart_kernel(
-  const longlong2* __restrict__ in_pairs, const int64_t* __restrict__ keys,
-  const int64_t* __restrict__ pay, const int64_t* __restrict__ segoff, int B, int F,
-  longlong2* __restrict__ out_pairs, int64_t* __restrict__ bucket_offsets /* B+1 */)
-{
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  longlong2* tbuf = (longlong2*)smem;
-  uint32_t* hist = (uint32_t*)(tbuf + SCATTER_TILE);
-  uint32_t* base = hist + F;
-  uint32_t* gcur = base + F;
-  uint32_t* seghist = gcur + F;
-  const int tid = threadIdx.x;
-  const int a = blockIdx.x;
-  const int64_t s0 = segoff[a], s1 = segoff[a + 1];
-  if (tid < F) seghist[tid] = 0;
-  __syncthreads();
-  for (int64_t i = s0 + tid; i < s1; i += blockDim.x) {
-    int64_t k = SINGLE_LEVEL ? nt_load(&keys[i]) : nt_load(&in_pairs[i].x);
-    atomicAdd(&seghist[subF_of(k, F)], 1u);
+/* Block g owns pass-A group g: it reads the group's rows from one or more
+ * input segments and writes them, grouped into F sub-buckets (runtime power
+ * of two <= 1024, subF_of bit fields disjoint from the pass-A group bits),
+ * as one compact run starting at group_base[g] — emitting the final bucket
+ * offsets on the way. Segs names the block's input segments. */
+struct ListSegs {  // segment sgi of group g: bounds[sgi][g] .. bounds[sgi][g+1]
+  const int64_t* bounds;  // [nseg][PA+1] absolute row offsets
+  int nseg, PA, g;
+  __device__ __forceinline__ int count() const { return nseg; }
+  __device__ __forceinline__ int64_t lo(int sgi) const
+  {
+    return bounds[(size_t)sgi * (PA + 1) + g];
   }
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t acc = 0;
-    for (int j = 0; j < F; j++) {
-      uint32_t c = seghist[j];
-      gcur[j] = (uint32_t)s0 + acc;
-      bucket_offsets[(size_t)a * F + j] = s0 + acc;
-      acc += c;
-    }
-    if (a == gridDim.x - 1) bucket_offsets[B] = s1;
+  __device__ __forceinline__ int64_t hi(int sgi) const
+  {
+    return bounds[(size_t)sgi * (PA + 1) + g + 1];
   }
-  __syncthreads();
-  staged_scatter_span<1, SINGLE_LEVEL>(keys, pay, in_pairs, s0, s1, F, tbuf, hist, base, gcur,
-                                       out_pairs);
-}
+};
+struct OneSeg {
+  int64_t s0, s1;
+  __device__ __forceinline__ int count() const { return 1; }
+  __device__ __forceinline__ int64_t lo(int) const { return s0; }
+  __device__ __forceinline__ int64_t hi(int) const { return s1; }
+};
 
-/* pass B over per-peer segment lists (fused wire path): block = one pass-A
- * group g, whose rows arrived pre-grouped inside each peer slice; the
- * block's sub-buckets fan out by F (runtime power of two). */
-__global__ __launch_bounds__(BUCKET_THREADS) void subpart_lists_kernel(
-  const int64_t* __restrict__ keys, const int64_t* __restrict__ pay,
-  const int64_t* __restrict__ seg_bounds /* [nseg][PA+1] absolute row offsets */, int nseg,
-  int PA, int F, const int64_t* __restrict__ group_base /* [PA+1] output bases */,
-  longlong2* __restrict__ out_pairs, int64_t* __restrict__ bucket_offsets /* PA*F+1 */)
+/* the pass-B prologue: histogram the group's rows by sub-bucket (seghist), scan
+ * serially on thread 0, write bucket_offsets[g*F .. g*F+F) and seed the
+ * global cursors gcur; the last block closes bucket_offsets[gridDim*F] with
+ * group_base[gridDim] */
+template <class Rows, class Segs>
+__device__ __forceinline__ void subpart_prologue(Rows in, Segs segs, int F,
+                                                 const int64_t* group_base, const StagedLds& l,
+                                                 int64_t* bucket_offsets,
+                                                 const unsigned nthreads)
 {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  longlong2* tbuf = (longlong2*)smem;
-  uint32_t* hist = (uint32_t*)(tbuf + SCATTER_TILE);
-  uint32_t* base = hist + F;
-  uint32_t* gcur = base + F;
-  uint32_t* seghist = gcur + F;
   const int tid = threadIdx.x;
   const int g = blockIdx.x;
-  for (int j = tid; j < F; j += blockDim.x) seghist[j] = 0;
+  for (int j = tid; j < F; j += nthreads) l.seghist[j] = 0;
   __syncthreads();
-  for (int sgi = 0; sgi < nseg; sgi++) {
-    const int64_t s0 = seg_bounds[(size_t)sgi * (PA + 1) + g];
-    const int64_t s1 = seg_bounds[(size_t)sgi * (PA + 1) + g + 1];
-    for (int64_t i = s0 + tid; i < s1; i += blockDim.x)
-      atomicAdd(&seghist[subF_of(nt_load(&keys[i]), F)], 1u);
+  for (int sgi = 0; sgi < segs.count(); sgi++) {
+    const int64_t s0 = segs.lo(sgi), s1 = segs.hi(sgi);
+    for (int64_t i = s0 + tid; i < s1; i += nthreads)
+      atomicAdd(&l.seghist[subF_of(in.key(i), F)], 1u);
   }
   __syncthreads();
   if (tid == 0) {
     uint32_t acc = 0;
     const int64_t gb = group_base[g];
     for (int j = 0; j < F; j++) {
-      uint32_t c = seghist[j];
-      gcur[j] = (uint32_t)(gb + acc);
+      uint32_t c = l.seghist[j];
+      l.gcur[j] = (uint32_t)(gb + acc);
       bucket_offsets[(size_t)g * F + j] = gb + acc;
       acc += c;
     }
-    if (g == gridDim.x - 1) bucket_offsets[(size_t)PA * F] = group_base[PA];
+    if (g == gridDim.x - 1) bucket_offsets[(size_t)gridDim.x * F] = group_base[gridDim.x];
   }
   __syncthreads();
-  for (int sgi = 0; sgi < nseg; sgi++) {
-    const int64_t s0 = seg_bounds[(size_t)sgi * (PA + 1) + g];
-    const int64_t s1 = seg_bounds[(size_t)sgi * (PA + 1) + g + 1];
-    staged_scatter_span<1, true>(keys, pay, nullptr, s0, s1, F, tbuf, hist, base, gcur,
-                                 out_pairs);
-  }
+}
+
+/* one pass-B block: prologue, then the staged scatter of each segment */
+template <class Rows, class Segs>
+__device__ __forceinline__ void subpart_block(Rows in, Segs segs, int F,
+                                              const int64_t* group_base, longlong2* out_pairs,
+                                              int64_t* bucket_offsets,
+                                              const unsigned nthreads)
+{
+  const StagedLds l = staged_lds_carve(F);
+  subpart_prologue(in, segs, F, group_base, l, bucket_offsets, nthreads);
+  for (int sgi = 0; sgi < segs.count(); sgi++)
+    staged_scatter_span(in, segs.lo(sgi), segs.hi(sgi), PlaceSubF{F}, l, PairSink{out_pairs},
+                        nthreads);
+}
+
+/* columns in, over per-peer segment lists (fused wire path: the group's rows
+ * arrived pre-grouped inside each peer slice; grid = PA), and the B == 256
+ * single-group case of bucket_partition2 (nseg = PA = 1, segoff = {0, n} as
+ * both bounds and bases) */
+__global__ __launch_bounds__(BUCKET_THREADS) void subpart_lists_kernel(
+  const int64_t* __restrict__ keys, const int64_t* __restrict__ pay,
+  const int64_t* __restrict__ seg_bounds /* [nseg][PA+1] absolute row offsets */, int nseg,
+  int PA, int F, const int64_t* __restrict__ group_base /* [PA+1] output bases */,
+  longlong2* __restrict__ out_pairs, int64_t* __restrict__ bucket_offsets /* PA*F+1 */)
+{
+  subpart_block(ColumnRows{keys, pay}, ListSegs{seg_bounds, nseg, PA, (int)blockIdx.x}, F,
+                group_base, out_pairs, bucket_offsets, blockDim.x);
+}
+
+/* pairs in, over the exact pass-A segments [segoff[a], segoff[a+1]), which
+ * are also the output bases (grid = PA) */
+__global__ __launch_bounds__(BUCKET_THREADS) void bucket_subpart_kernel(
+  const longlong2* __restrict__ in_pairs, const int64_t* __restrict__ segoff /* PA+1 */, int F,
+  longlong2* __restrict__ out_pairs, int64_t* __restrict__ bucket_offsets /* PA*F+1 */)
+{
+  const int a = blockIdx.x;
+  subpart_block(PairRows{in_pairs}, OneSeg{segoff[a], segoff[a + 1]}, F, segoff, out_pairs,
+                bucket_offsets, blockDim.x);
+}
+
+/* pairs in, over slack pass-A segments: block a reads [a*capA, a*capA+len[a])
+ * and writes its sub-buckets compactly at segout[a] (exclusive scan of the
+ * lengths), so bucket_offsets keep the contiguous PA*F+1 convention that
+ * lds_join consumes (grid = PA) */
+__global__ __launch_bounds__(BUCKET_THREADS) void bucket_subpart_slack_kernel(
+  const longlong2* __restrict__ in_pairs, const uint32_t* __restrict__ seg_len, int64_t capA,
+  const int64_t* __restrict__ segout /* PA+1 compact output bases */, int F,
+  longlong2* __restrict__ out_pairs, int64_t* __restrict__ bucket_offsets /* PA*F+1 */)
+{
+  const int64_t s0 = (int64_t)blockIdx.x * capA;
+  subpart_block(PairRows{in_pairs}, OneSeg{s0, s0 + seg_len[blockIdx.x]}, F, segout, out_pairs,
+                bucket_offsets, blockDim.x);
 }
 
 void subpart_lists(const int64_t* d_keys, const int64_t* d_pay, const int64_t* d_seg_bounds,
@@ -1142,11 +1234,9 @@ void subpart_lists(const int64_t* d_keys, const int64_t* d_pay, const int64_t* d
 {
   DJ_CHECK_ERROR(F >= 64 && F <= 1024 && (F & (F - 1)) == 0,
                  "subpart_lists: F must be a power of two in [64,1024]");
-  size_t lds = SCATTER_TILE * sizeof(longlong2) + 4 * (size_t)F * 4;
-  hipLaunchKernelGGL(subpart_lists_kernel, dim3(PA), dim3(BUCKET_THREADS), lds, s, d_keys,
-                     d_pay, d_seg_bounds, nseg, PA, F, d_group_base, d_out_pairs,
-                     d_bucket_offsets);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(subpart_lists_kernel, dim3(PA), dim3(BUCKET_THREADS),
+            staged_lds_bytes(F, kPassBTables), s, d_keys, d_pay, d_seg_bounds, nseg, PA, F,
+            d_group_base, d_out_pairs, d_bucket_offsets);
 }
 
 /* ---- fused per-bucket LDS build + single-pass probe with staged output ----
@@ -1168,26 +1258,26 @@ void subpart_lists(const int64_t* d_keys, const int64_t* d_pay, const int64_t* d
  * 131072 buckets; a single hot counter absorbs one wave-op per ~12 ns);
  * accumulating the stage across buckets and flushing at the 3/4 watermark
  * (or group end) cuts the atomics ~4x: 1.69 -> 1.35 ms measured
- * (experiments/join_v2/v4). Stage spills (high-duplication buckets, or a
+ * (DESIGN.md §3). Stage spills (high-duplication buckets, or a
  * bucket landing on a nearly-full stage at high selectivity) go straight to
  * the global counter (plain per-match atomic: the compiler wave-aggregates
  * it; a hand-ballot version of this spill path — even though it never
  * executes at sel 0.3 — cost 1.0 ms of probe-walk codegen, 2.42 vs 1.41 ms,
- * experiments/join_v6).
+ * DESIGN.md §3 "the codegen cliff", profiles/r02_join_factorial.log).
  *
  * Bucket input layout: SLACK=false — compact offsets (loff/roff, B+1);
- * SLACK=true — the slack layout of bucket_partition2_slack
+ * SLACK=true — the slack layout of bucket_partition2_slack_pair
  * (b*capL + llen[b]). Compile-time split for the same reason.
  *
- * KBUK > 1 contract: B MUST be a multiple of KBUK with llen/rlen (or
+ * KBUK contract: B MUST be a multiple of KBUK with llen/rlen (or
  * loff/roff) valid over all of it — callers pad with zero-length buckets
- * (lds_join_slack checks). Padding keeps every flush-slot comparison
- * against the constant KBUK-1: the b >= B tail break, a dynamic flush-slot
- * register, and an in-range guard each put the kernel back at ~2.35 ms
- * (experiments/join_v7 factorial; the goto-drain structure below measured
- * 1.40 ms). KBUK == 1 (only for a compact B that is not a multiple of 4 —
- * no current caller produces one) flushes every bucket — the r1 behavior,
- * ~0.3 ms slower per 100 M rows but contract-free. */
+ * (lds_join and lds_join_slack check). Padding keeps every flush-slot
+ * comparison against the constant KBUK-1: the b >= B tail break, a dynamic
+ * flush-slot register, and an in-range guard each put the kernel back at
+ * ~2.35 ms (profiles/r02_join_factorial.log; the goto-drain structure below
+ * measured 1.40 ms). Only KBUK == 4 is instantiated; the KBUK == 1 branches
+ * in the body (flush every bucket, the r1 behavior, ~0.3 ms slower per
+ * 100 M rows) fold away. */
 template <int SLOTS2, bool SLACK, int KBUK>
 __global__ __launch_bounds__(BUCKET_THREADS) void lds_join_kernel(
   const longlong2* __restrict__ lrows, const int64_t* __restrict__ loff,
@@ -1342,6 +1432,17 @@ __device__ __forceinline__ uint32_t fused_pid(int64_t key, int nparts_rank, uint
   return p * (uint32_t)PA + g;
 }
 
+struct PlaceFused {  // fused_pid over nparts_rank * PA slices
+  int nparts_rank;
+  uint32_t seed;
+  int PA;
+  __device__ __forceinline__ int fanout() const { return nparts_rank * PA; }
+  __device__ __forceinline__ uint32_t operator()(int64_t key) const
+  {
+    return fused_pid(key, nparts_rank, seed, PA);
+  }
+};
+
 __global__ __launch_bounds__(BUCKET_THREADS) void fused_count_kernel(
   const int64_t* __restrict__ keys, int64_t n, int nparts_rank, uint32_t seed, int PA,
   uint32_t* __restrict__ counts)
@@ -1367,64 +1468,8 @@ __global__ __launch_bounds__(BUCKET_THREADS) void fused_scatter_kernel(
   const int64_t* __restrict__ offsets, int64_t* __restrict__ out_keys,
   int64_t* __restrict__ out_pay)
 {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  longlong2* tbuf = (longlong2*)smem;
-  const int P = nparts_rank * PA;
-  uint32_t* hist = (uint32_t*)(tbuf + SCATTER_TILE);
-  uint32_t* base = hist + P;
-  uint32_t* gcur = base + P;
-  const int tid = threadIdx.x;
-  if (tid < P)
-    gcur[tid] = (uint32_t)offsets[tid] + counts[(size_t)blockIdx.x * P + tid];
-  __syncthreads();
-  const int64_t chunk = (n + gridDim.x - 1) / gridDim.x;
-  const int64_t start = (int64_t)blockIdx.x * chunk;
-  const int64_t end = min(start + chunk, n);
-  constexpr int VPT = SCATTER_TILE / BUCKET_THREADS;
-  for (int64_t t0 = start; t0 < end; t0 += SCATTER_TILE) {
-    const int count = (int)min((int64_t)SCATTER_TILE, end - t0);
-    if (tid < P) hist[tid] = 0;
-    __syncthreads();
-    longlong2 r[VPT];
-    uint32_t g[VPT], rank[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; v++) {
-      int64_t i = t0 + (int64_t)v * blockDim.x + tid;
-      if (i < end) {
-        r[v].x = nt_load(&keys[i]);
-        r[v].y = pay ? nt_load(&pay[i]) : i;
-        g[v] = fused_pid(r[v].x, nparts_rank, seed, PA);
-        rank[v] = atomicAdd(&hist[g[v]], 1u);
-      }
-    }
-    __syncthreads();
-    if (tid < P) base[tid] = hist[tid];
-    __syncthreads();
-    for (int off = 1; off < P; off <<= 1) {
-      uint32_t add = (tid < P && tid >= off) ? base[tid - off] : 0;
-      __syncthreads();
-      if (tid < P) base[tid] += add;
-      __syncthreads();
-    }
-    if (tid < P) base[tid] -= hist[tid];
-    __syncthreads();
-#pragma unroll
-    for (int v = 0; v < VPT; v++) {
-      int64_t i = t0 + (int64_t)v * blockDim.x + tid;
-      if (i < end) tbuf[base[g[v]] + rank[v]] = r[v];
-    }
-    __syncthreads();
-    for (int pos = tid; pos < count; pos += blockDim.x) {
-      longlong2 row = tbuf[pos];
-      uint32_t gg = fused_pid(row.x, nparts_rank, seed, PA);
-      uint32_t dst = gcur[gg] + (uint32_t)(pos - base[gg]);
-      out_keys[dst] = row.x;
-      out_pay[dst] = row.y;
-    }
-    __syncthreads();
-    if (tid < P) gcur[tid] += hist[tid];
-    __syncthreads();
-  }
+  chunk_scatter(keys, pay, n, PlaceFused{nparts_rank, seed, PA}, counts, offsets,
+                ColumnSink{out_keys, out_pay}, blockDim.x);
 }
 
 void fused_partition(const int64_t* d_keys, const int64_t* d_pay, int64_t n, int nparts_rank,
@@ -1435,21 +1480,13 @@ void fused_partition(const int64_t* d_keys, const int64_t* d_pay, int64_t n, int
   const int P = nparts_rank * PA;
   DJ_CHECK_ERROR(P >= 1 && P <= 1024, "fused_partition: nparts_rank*PA must be <= 1024");
   DJ_CHECK_ERROR(n < (int64_t)UINT32_MAX, "fused_partition: n must be < 2^32");
-  size_t hist_lds = (size_t)P * 4;
-  size_t scatter_lds = SCATTER_TILE * sizeof(longlong2) + 3 * hist_lds;
-  hipLaunchKernelGGL(fused_count_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS), hist_lds,
-                     s, d_keys, n, nparts_rank, seed, PA, d_counts);
-  DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(bucket_scanA_kernel, dim3(P), dim3(BUCKET_BLOCKS), 0, s, d_counts, P,
-                     d_totals);
-  DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(bucket_scanB_kernel, dim3(1), dim3(BUCKET_THREADS), 0, s, d_totals, P,
-                     d_offsets);
-  DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(fused_scatter_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS),
-                     scatter_lds, s, d_keys, d_pay, n, nparts_rank, seed, PA, d_counts,
-                     d_offsets, d_out_keys, d_out_pay);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(fused_count_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS), count_lds_bytes(P),
+            s, d_keys, n, nparts_rank, seed, PA, d_counts);
+  DJ_LAUNCH(bucket_scanA_kernel, dim3(P), dim3(BUCKET_BLOCKS), 0, s, d_counts, P, d_totals);
+  DJ_LAUNCH(bucket_scanB_kernel, dim3(1), dim3(BUCKET_THREADS), 0, s, d_totals, P, d_offsets);
+  DJ_LAUNCH(fused_scatter_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS),
+            staged_lds_bytes(P, kPassATables), s, d_keys, d_pay, n, nparts_rank, seed, PA,
+            d_counts, d_offsets, d_out_keys, d_out_pay);
 }
 
 /* ---- slack pass A (local non-stable partition): per-tile global atomic
@@ -1462,6 +1499,12 @@ void fused_partition(const int64_t* d_keys, const int64_t* d_pay, int64_t n, int
  * slack — SKIPS rows and sets bit 2 of any_overflow; the caller must then
  * redo the whole join (the partition output is incomplete). */
 constexpr int SLACK_TILE = 8192;
+/* LDS of the slack kernels, as slackA_body and slackB_body carve it: the
+ * tile buffer, hist/base/gcur/glim u32[P] and the wave-scan partials u32[16] */
+static size_t slack_lds_bytes(int tile_rows, int P)
+{
+  return (size_t)tile_rows * sizeof(longlong2) + 4 * (size_t)P * sizeof(uint32_t) + 64;
+}
 
 /* block-level exclusive scan of hist[0..P) into base[0..P) via per-wave
  * shfl scans + one cross-wave partial pass (2 barriers; the Hillis-Steele
@@ -1500,7 +1543,7 @@ __device__ __forceinline__ void wave_excl_scan(const uint32_t* hist, uint32_t* b
  * lane issue BEFORE the current tile's flush, so the HBM load latency hides
  * under the store burst (this kernel runs 1 block/CU, so barriered phases
  * cannot overlap across blocks; measured 0.90 -> ~0.86 ms/table with the
- * wave scans, experiments/join_v4). */
+ * wave scans). */
 __device__ __forceinline__ void slackA_body(
   const int64_t* __restrict__ keys, const int64_t* __restrict__ pay, int64_t n, int P,
   int64_t capA, uint32_t* __restrict__ gcursor, int* __restrict__ any_overflow,
@@ -1630,46 +1673,6 @@ __global__ void clamp_seglen_kernel(uint32_t* seg_len, int P, uint32_t capA)
   if (i < P && seg_len[i] > capA) seg_len[i] = capA;
 }
 
-/* pass B over slack pass-A segments: block a reads [a*capA, a*capA+len[a])
- * and writes its sub-buckets compactly at segout[a] (exclusive scan of the
- * lengths), so bucket_offsets keep the contiguous B+1 convention that
- * lds_join consumes. */
-__global__ __launch_bounds__(BUCKET_THREADS) void bucket_subpart_slack_kernel(
-  const longlong2* __restrict__ in_pairs, const uint32_t* __restrict__ seg_len, int64_t capA,
-  const int64_t* __restrict__ segout /* PA+1 compact output bases */, int B, int F,
-  longlong2* __restrict__ out_pairs, int64_t* __restrict__ bucket_offsets /* B+1 */)
-{
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  longlong2* tbuf = (longlong2*)smem;
-  uint32_t* hist = (uint32_t*)(tbuf + SCATTER_TILE);
-  uint32_t* base = hist + F;
-  uint32_t* gcur = base + F;
-  uint32_t* seghist = gcur + F;
-  const int tid = threadIdx.x;
-  const int a = blockIdx.x;
-  const int64_t s0 = (int64_t)a * capA;
-  const int64_t s1 = s0 + seg_len[a];
-  const int64_t ob = segout[a];
-  if (tid < F) seghist[tid] = 0;
-  __syncthreads();
-  for (int64_t i = s0 + tid; i < s1; i += blockDim.x)
-    atomicAdd(&seghist[subF_of(nt_load(&in_pairs[i].x), F)], 1u);
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t acc = 0;
-    for (int j = 0; j < F; j++) {
-      uint32_t c = seghist[j];
-      gcur[j] = (uint32_t)(ob + acc);
-      bucket_offsets[(size_t)a * F + j] = ob + acc;
-      acc += c;
-    }
-    if (a == gridDim.x - 1) bucket_offsets[B] = segout[gridDim.x];
-  }
-  __syncthreads();
-  staged_scatter_span<1, false>(nullptr, nullptr, in_pairs, s0, s1, F, tbuf, hist, base, gcur,
-                                out_pairs);
-}
-
 /* pass B without the count sweep (round 2): block = pass-A group a reads its
  * slack segment [a*capA, a*capA+seg_len[a]) and scatters into F per-bucket
  * SLACK segments at analytic starts b*capB with LDS cursors (only this
@@ -1678,7 +1681,7 @@ __global__ __launch_bounds__(BUCKET_THREADS) void bucket_subpart_slack_kernel(
  * latency hides under the store burst. Bucket lengths out in d_lens.
  * BTILE 8192 (1 block/CU) measured 0.88 vs 1.01 ms/table over the 4096
  * 2-block tile, and per-bucket limits are precomputed in LDS (glim) so the
- * flush bound check pays no per-row 64-bit multiply (experiments/join_v7). */
+ * flush bound check pays no per-row 64-bit multiply. */
 constexpr int BTILE = 8192;  // pass-B staging tile (128 KiB, 1 block/CU)
 __device__ __forceinline__ void slackB_body(
   const longlong2* __restrict__ in_pairs, const uint32_t* __restrict__ seg_len, int64_t capA,
@@ -1775,14 +1778,6 @@ __device__ __forceinline__ void slackB_body(
   if (tid == 0 && s_ovf) atomicOr(any_overflow, 2);
 }
 
-__global__ __launch_bounds__(BUCKET_THREADS) void bucket_subpart_slack2_kernel(
-  const longlong2* __restrict__ in_pairs, const uint32_t* __restrict__ seg_len, int64_t capA,
-  int F, int64_t capB, longlong2* __restrict__ out_pairs, uint32_t* __restrict__ lens,
-  int* __restrict__ any_overflow)
-{
-  slackB_body(in_pairs, seg_len, capA, F, capB, out_pairs, lens, any_overflow, blockIdx.x);
-}
-
 /* both tables in ONE launch (grid = 2*PA; see bucket_scatter_slack_pair) */
 __global__ __launch_bounds__(BUCKET_THREADS) void bucket_subpart_slack2_pair_kernel(
   const longlong2* __restrict__ in0, const uint32_t* __restrict__ seg0, int64_t capA0,
@@ -1820,8 +1815,6 @@ void bucket_partition2_slack_pair(const int64_t* d_k0, const int64_t* d_p0, int6
                    (int64_t)B * capB0 < (int64_t)UINT32_MAX &&
                    (int64_t)B * capB1 < (int64_t)UINT32_MAX,
                  "bucket_partition_slack: slack layout exceeds u32 row index");
-  size_t scatter_lds = SLACK_TILE * sizeof(longlong2) + 4 * (size_t)PA * sizeof(uint32_t) + 64;
-  size_t sub_lds = BTILE * sizeof(longlong2) + 4 * (size_t)F * sizeof(uint32_t) + 64;
   DJ_HIP_CALL(hipMemsetAsync(d_cur0, 0, (size_t)PA * 4, s));
   DJ_HIP_CALL(hipMemsetAsync(d_cur1, 0, (size_t)PA * 4, s));
   /* grid split proportional to table sizes (TPC-H joins 60M x 240M; an
@@ -1829,50 +1822,16 @@ void bucket_partition2_slack_pair(const int64_t* d_k0, const int64_t* d_p0, int6
   int blocks0 = (int)(2.0 * BUCKET_BLOCKS * (double)n0 / (double)(n0 + n1) + 0.5);
   if (blocks0 < 1) blocks0 = 1;
   if (blocks0 > 2 * BUCKET_BLOCKS - 1) blocks0 = 2 * BUCKET_BLOCKS - 1;
-  hipLaunchKernelGGL(bucket_scatter_slack_pair_kernel, dim3(2 * BUCKET_BLOCKS),
-                     dim3(BUCKET_THREADS), scatter_lds, s, d_k0, d_p0, n0, capA0, d_cur0,
-                     d_tmp0, d_k1, d_p1, n1, capA1, d_cur1, d_tmp1, PA, blocks0,
-                     d_any_overflow);
-  DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(clamp_seglen_kernel, dim3((PA + 255) / 256), dim3(256), 0, s, d_cur0,
-                     PA, (uint32_t)capA0);
-  hipLaunchKernelGGL(clamp_seglen_kernel, dim3((PA + 255) / 256), dim3(256), 0, s, d_cur1,
-                     PA, (uint32_t)capA1);
-  DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(bucket_subpart_slack2_pair_kernel, dim3(2 * PA), dim3(BUCKET_THREADS),
-                     sub_lds, s, d_tmp0, d_cur0, capA0, capB0, d_out0, d_len0, d_tmp1,
-                     d_cur1, capA1, capB1, d_out1, d_len1, F, d_any_overflow);
-  DJ_HIP_CALL(hipGetLastError());
-}
-
-void bucket_partition2_slack(const int64_t* d_keys, const int64_t* d_pay, int64_t n, int B,
-                             longlong2* d_tmp_pairs, uint32_t* d_cursors, int64_t capB,
-                             longlong2* d_out_pairs, uint32_t* d_lens, int* d_any_overflow,
-                             hipStream_t s)
-{
-  DJ_CHECK_ERROR(n < (int64_t)UINT32_MAX, "bucket_partition_slack: n must be < 2^32");
-  const int PA = bucket_groups_for(B);
-  const int F = B / PA;
-  const int64_t capA = slack_capA(n, PA);
-  DJ_CHECK_ERROR(PA >= 2 && PA <= 1024 && F >= 1 && F <= 1024,
-                 "bucket_partition_slack: B out of range (PA must be >= 2)");
-  DJ_CHECK_ERROR((int64_t)PA * capA + n < (int64_t)UINT32_MAX &&
-                   (int64_t)B * capB < (int64_t)UINT32_MAX,
-                 "bucket_partition_slack: slack layout exceeds u32 row index");
-  size_t scatter_lds = SLACK_TILE * sizeof(longlong2) + 4 * (size_t)PA * sizeof(uint32_t) + 64;
-  size_t sub_lds = BTILE * sizeof(longlong2) + 4 * (size_t)F * sizeof(uint32_t) + 64;
-  DJ_HIP_CALL(hipMemsetAsync(d_cursors, 0, (size_t)PA * 4, s));
-  hipLaunchKernelGGL(bucket_scatter_slack_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS),
-                     scatter_lds, s, d_keys, d_pay, n, PA, capA, d_cursors, d_any_overflow,
-                     d_tmp_pairs);
-  DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(clamp_seglen_kernel, dim3((PA + 255) / 256), dim3(256), 0, s, d_cursors,
-                     PA, (uint32_t)capA);
-  DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(bucket_subpart_slack2_kernel, dim3(PA), dim3(BUCKET_THREADS), sub_lds, s,
-                     d_tmp_pairs, d_cursors, capA, F, capB, d_out_pairs, d_lens,
-                     d_any_overflow);
-  DJ_HIP_CALL(hipGetLastError());
+  DJ_LAUNCH(bucket_scatter_slack_pair_kernel, dim3(2 * BUCKET_BLOCKS), dim3(BUCKET_THREADS),
+            slack_lds_bytes(SLACK_TILE, PA), s, d_k0, d_p0, n0, capA0, d_cur0, d_tmp0, d_k1,
+            d_p1, n1, capA1, d_cur1, d_tmp1, PA, blocks0, d_any_overflow);
+  DJ_LAUNCH(clamp_seglen_kernel, dim3((PA + 255) / 256), dim3(256), 0, s, d_cur0, PA,
+            (uint32_t)capA0);
+  DJ_LAUNCH(clamp_seglen_kernel, dim3((PA + 255) / 256), dim3(256), 0, s, d_cur1, PA,
+            (uint32_t)capA1);
+  DJ_LAUNCH(bucket_subpart_slack2_pair_kernel, dim3(2 * PA), dim3(BUCKET_THREADS),
+            slack_lds_bytes(BTILE, F), s, d_tmp0, d_cur0, capA0, capB0, d_out0, d_len0, d_tmp1,
+            d_cur1, capA1, capB1, d_out1, d_len1, F, d_any_overflow);
 }
 
 void bucket_partition2(const int64_t* d_keys, const int64_t* d_pay, int64_t n, int B,
@@ -1885,56 +1844,45 @@ void bucket_partition2(const int64_t* d_keys, const int64_t* d_pay, int64_t n, i
   const int F = B / PA;
   DJ_CHECK_ERROR(PA >= 1 && PA <= 1024 && F >= 1 && F <= 1024,
                  "bucket_partition: B out of range");
-  const size_t subpart_lds =
-    SCATTER_TILE * sizeof(longlong2) + 4 * (size_t)F * sizeof(uint32_t);
+  const size_t subpart_lds = staged_lds_bytes(F, kPassBTables);
   if (PA == 1) {
-    hipLaunchKernelGGL(set_segoff1_kernel, dim3(1), dim3(1), 0, s, d_segoff, n);
-    DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(bucket_subpart_kernel<true>, dim3(PA), dim3(BUCKET_THREADS),
-                       subpart_lds, s, (const longlong2*)nullptr, d_keys, d_pay, d_segoff, B,
-                       F, d_out_pairs, d_offsets);
-    DJ_HIP_CALL(hipGetLastError());
+    /* single group: pass B alone, straight from the input columns, with
+     * segoff = {0, n} as both its one segment's bounds and its output bases */
+    DJ_LAUNCH(set_segoff1_kernel, dim3(1), dim3(1), 0, s, d_segoff, n);
+    DJ_LAUNCH(subpart_lists_kernel, dim3(1), dim3(BUCKET_THREADS), subpart_lds, s, d_keys,
+              d_pay, d_segoff, 1, 1, F, d_segoff, d_out_pairs, d_offsets);
   } else if (d_any_overflow != nullptr &&
              (int64_t)PA * slack_capA(n, PA) + n < (int64_t)UINT32_MAX) {
     /* slack path: no count pass (see bucket_scatter_slack_kernel header) */
     const int64_t capA = slack_capA(n, PA);
-    size_t scatter_lds = SLACK_TILE * sizeof(longlong2) + 4 * (size_t)PA * sizeof(uint32_t) + 64;
     DJ_HIP_CALL(hipMemsetAsync(d_totals, 0, (size_t)PA * 4, s));
-    hipLaunchKernelGGL(bucket_scatter_slack_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS),
-                       scatter_lds, s, d_keys, d_pay, n, PA, capA, d_totals, d_any_overflow,
-                       d_tmp_pairs);
-    DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(clamp_seglen_kernel, dim3((PA + 255) / 256), dim3(256), 0, s, d_totals,
-                       PA, (uint32_t)capA);
-    DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(bucket_scanB_kernel, dim3(1), dim3(BUCKET_THREADS), 0, s, d_totals, PA,
-                       d_segoff);
-    DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(bucket_subpart_slack_kernel, dim3(PA), dim3(BUCKET_THREADS), subpart_lds,
-                       s, d_tmp_pairs, d_totals, capA, d_segoff, B, F, d_out_pairs, d_offsets);
-    DJ_HIP_CALL(hipGetLastError());
+    DJ_LAUNCH(bucket_scatter_slack_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS),
+              slack_lds_bytes(SLACK_TILE, PA), s, d_keys, d_pay, n, PA, capA, d_totals,
+              d_any_overflow, d_tmp_pairs);
+    DJ_LAUNCH(clamp_seglen_kernel, dim3((PA + 255) / 256), dim3(256), 0, s, d_totals, PA,
+              (uint32_t)capA);
+    DJ_LAUNCH(bucket_scanB_kernel, dim3(1), dim3(BUCKET_THREADS), 0, s, d_totals, PA,
+              d_segoff);
+    DJ_LAUNCH(bucket_subpart_slack_kernel, dim3(PA), dim3(BUCKET_THREADS), subpart_lds, s,
+              d_tmp_pairs, d_totals, capA, d_segoff, F, d_out_pairs, d_offsets);
   } else {
-    size_t hist_lds = (size_t)PA * sizeof(uint32_t);
-    size_t scatter_lds = SCATTER_TILE * sizeof(longlong2) + 3 * hist_lds;
-    hipLaunchKernelGGL(bucket_count_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS), hist_lds,
-                       s, d_keys, n, PA, d_counts);
-    DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(bucket_scanA_kernel, dim3(PA), dim3(BUCKET_BLOCKS), 0, s, d_counts, PA,
-                       d_totals);
-    DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(bucket_scanB_kernel, dim3(1), dim3(BUCKET_THREADS), 0, s, d_totals, PA,
-                       d_segoff);
-    DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(bucket_scatter_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS),
-                       scatter_lds, s, d_keys, d_pay, n, PA, d_counts, d_segoff, d_tmp_pairs);
-    DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(bucket_subpart_kernel<false>, dim3(PA), dim3(BUCKET_THREADS),
-                       subpart_lds, s, d_tmp_pairs, (const int64_t*)nullptr,
-                       (const int64_t*)nullptr, d_segoff, B, F, d_out_pairs, d_offsets);
-    DJ_HIP_CALL(hipGetLastError());
+    /* exact path: counted pass A, then pass B over its exact segments */
+    DJ_LAUNCH(bucket_count_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS),
+              count_lds_bytes(PA), s, d_keys, n, PA, d_counts);
+    DJ_LAUNCH(bucket_scanA_kernel, dim3(PA), dim3(BUCKET_BLOCKS), 0, s, d_counts, PA,
+              d_totals);
+    DJ_LAUNCH(bucket_scanB_kernel, dim3(1), dim3(BUCKET_THREADS), 0, s, d_totals, PA,
+              d_segoff);
+    DJ_LAUNCH(bucket_scatter_kernel, dim3(BUCKET_BLOCKS), dim3(BUCKET_THREADS),
+              staged_lds_bytes(PA, kPassATables), s, d_keys, d_pay, n, PA, d_counts, d_segoff,
+              d_tmp_pairs);
+    DJ_LAUNCH(bucket_subpart_kernel, dim3(PA), dim3(BUCKET_THREADS), subpart_lds, s,
+              d_tmp_pairs, d_segoff, F, d_out_pairs, d_offsets);
   }
 }
 
+/* flush groups of 4 buckets (lds_join_kernel's KBUK contract): both entry
+ * points below require B % 4 == 0 */
 static void lds_join_launch(const longlong2* d_lrows, const int64_t* d_loff,
                             const uint32_t* d_llen, int64_t capL, const longlong2* d_rrows,
                             const int64_t* d_roff, const uint32_t* d_rlen, int64_t capR,
@@ -1945,36 +1893,20 @@ static void lds_join_launch(const longlong2* d_lrows, const int64_t* d_loff,
 {
   DJ_CHECK_ERROR(table_slots == 2048 || table_slots == 4096,
                  "lds_join: table_slots must be 2048 or 4096");
-  /* KBUK = 4 whenever B is a multiple of 4 — slack callers pad to it, and
-   * every compact caller's B already is (bucket_count_for powers of two,
-   * fused-wire PA*F). KBUK = 1 (flush per bucket, ~0.3 ms/100M slower)
-   * only for an unaligned compact B. */
   const bool slack = d_llen != nullptr;
-  const int kbuk = (slack || B % 4 == 0) ? 4 : 1;
-  int64_t groups = ((int64_t)B + kbuk - 1) / kbuk;
+  const int64_t groups = (int64_t)B / 4;
   int grid = (int)(groups < 8192 ? groups : 8192);
   size_t lds =
     (size_t)table_slots * sizeof(longlong2) + 4 * JOIN_STAGE_ROWS * sizeof(int64_t) + 16;
   auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(BUCKET_THREADS), lds, s, d_lrows, d_loff,
-                       d_llen, capL, d_rrows, d_roff, d_rlen, capR, B, d_out0, d_out1,
-                       d_out2, d_out3, cap, (unsigned long long*)d_counter, d_overflow_flags,
-                       d_any_overflow, d_error);
+    DJ_LAUNCH(kern, dim3(grid), dim3(BUCKET_THREADS), lds, s, d_lrows, d_loff, d_llen, capL,
+              d_rrows, d_roff, d_rlen, capR, B, d_out0, d_out1, d_out2, d_out3, cap,
+              (unsigned long long*)d_counter, d_overflow_flags, d_any_overflow, d_error);
   };
-  if (table_slots == 4096) {
-    if (slack)
-      launch(lds_join_kernel<4096, true, 4>);
-    else
-      kbuk == 4 ? launch(lds_join_kernel<4096, false, 4>)
-                : launch(lds_join_kernel<4096, false, 1>);
-  } else {
-    if (slack)
-      launch(lds_join_kernel<2048, true, 4>);
-    else
-      kbuk == 4 ? launch(lds_join_kernel<2048, false, 4>)
-                : launch(lds_join_kernel<2048, false, 1>);
-  }
-  DJ_HIP_CALL(hipGetLastError());
+  if (table_slots == 4096)
+    slack ? launch(lds_join_kernel<4096, true, 4>) : launch(lds_join_kernel<4096, false, 4>);
+  else
+    slack ? launch(lds_join_kernel<2048, true, 4>) : launch(lds_join_kernel<2048, false, 4>);
 }
 
 void lds_join(const longlong2* d_lrows, const int64_t* d_loff, const longlong2* d_rrows,
@@ -1982,6 +1914,8 @@ void lds_join(const longlong2* d_lrows, const int64_t* d_loff, const longlong2* 
               int64_t* d_out2, int64_t* d_out3, int64_t cap, int64_t* d_counter,
               uint32_t* d_overflow_flags, int* d_any_overflow, int* d_error, hipStream_t s)
 {
+  DJ_CHECK_ERROR(B % 4 == 0,
+                 "lds_join: B must be a multiple of 4 — see lds_join_kernel's KBUK contract");
   lds_join_launch(d_lrows, d_loff, nullptr, 0, d_rrows, d_roff, nullptr, 0, B, table_slots,
                   d_out0, d_out1, d_out2, d_out3, cap, d_counter, d_overflow_flags,
                   d_any_overflow, d_error, s);

@@ -123,23 +123,19 @@ void bucket_partition2(const int64_t* d_keys, const int64_t* d_pay, int64_t n, i
                        longlong2* d_tmp_pairs, uint32_t* d_counts, uint32_t* d_totals,
                        int64_t* d_segoff, int64_t* d_offsets, longlong2* d_out_pairs,
                        int* d_any_overflow, hipStream_t s);
-/* Count-free two-level slack partition (round 2, the product local-join
- * path): pass A as bucket_partition2's slack path, then pass B scatters each
- * group's rows into per-bucket SLACK segments at analytic starts
- * b*capB (capB = slack_capB(n, B)) with LDS cursors — no seghist sweep (the
- * r1 pass B fetched full 16 B lines just to histogram 8 B keys: 3.28 GB PMC
- * fetch vs 2.4 GB algorithmic). Bucket b holds d_lens[b] rows at
- * d_out_pairs[b*capB]. Overflow of any slack segment sets bit 2 of
- * *d_any_overflow (partition output incomplete -> caller redoes exactly).
- * Requires PA >= 2, n < 2^32, PA*slack_capA(n,PA)+... and B*capB < 2^32
- * (checked; errors loudly otherwise). d_tmp_pairs: longlong2[PA*capA];
- * d_cursors: u32[PA]. */
-void bucket_partition2_slack(const int64_t* d_keys, const int64_t* d_pay, int64_t n, int B,
-                             longlong2* d_tmp_pairs, uint32_t* d_cursors, int64_t capB,
-                             longlong2* d_out_pairs, uint32_t* d_lens, int* d_any_overflow,
-                             hipStream_t s);
-/* both tables through one pass-A and one pass-B launch (tail-wave fill);
- * needs a private tmp/cursor set per table */
+/* Count-free two-level slack partition of BOTH tables (round 2, the product
+ * local-join path): pass A as bucket_partition2's slack path, then pass B
+ * scatters each group's rows into per-bucket SLACK segments at analytic
+ * starts b*capB (capB = slack_capB(n, B)) with LDS cursors — no seghist sweep
+ * (the r1 pass B fetched full 16 B lines just to histogram 8 B keys: 3.28 GB
+ * PMC fetch vs 2.4 GB algorithmic). Bucket b of table t holds d_len<t>[b]
+ * rows at d_out<t>[b*capB<t>]. Both tables go through one pass-A and one
+ * pass-B launch (tail-wave fill), so each needs a private tmp/cursor set:
+ * d_tmp<t>: longlong2[PA*slack_capA(n<t>,PA)]; d_cur<t>: u32[PA]. Overflow of
+ * any slack segment sets bit 2 of *d_any_overflow (partition output
+ * incomplete -> caller redoes exactly). Requires PA >= 2, n < 2^32,
+ * PA*slack_capA(n,PA)+n and B*capB < 2^32 (checked; errors loudly
+ * otherwise). */
 void bucket_partition2_slack_pair(const int64_t* d_k0, const int64_t* d_p0, int64_t n0,
                                   longlong2* d_tmp0, uint32_t* d_cur0, int64_t capB0,
                                   longlong2* d_out0, uint32_t* d_len0, const int64_t* d_k1,
@@ -152,12 +148,15 @@ void bucket_partition2_slack_pair(const int64_t* d_k0, const int64_t* d_p0, int6
  * 4096 (1 block/CU, cap 3072 — for the fused wire path when the PA*F
  * fan-out cap leaves big buckets). Buckets whose build side exceeds the cap
  * set overflow_flags[b]/any_overflow and are skipped (host runs the
- * global-table path on them / redoes the batch). */
+ * global-table path on them / redoes the batch). Contract: B must be a
+ * multiple of 4 (the in-kernel flush-group size; every bucket_count_for and
+ * fused-wire PA*F is) — errors loudly otherwise. */
 void lds_join(const longlong2* d_lrows, const int64_t* d_loff, const longlong2* d_rrows,
               const int64_t* d_roff, int B, int table_slots, int64_t* d_out0, int64_t* d_out1,
               int64_t* d_out2, int64_t* d_out3, int64_t cap, int64_t* d_counter,
               uint32_t* d_overflow_flags, int* d_any_overflow, int* d_error, hipStream_t s);
-/* Same fused join over the slack bucket layout of bucket_partition2_slack:
+/* Same fused join over the slack bucket layout of
+ * bucket_partition2_slack_pair:
  * bucket b = d_lrows[b*capL .. +d_llen[b]) x d_rrows[b*capR .. +d_rlen[b]).
  * Contract: B must be a multiple of 4 (the in-kernel flush-group size) —
  * pad d_llen/d_rlen with zero-length buckets; errors loudly otherwise. */
