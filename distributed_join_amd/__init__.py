@@ -117,6 +117,14 @@ def lib():
             "dj_table_free": ([vp], None),
             "dj_gather_columns": ([vp, i32, vp, i64, i32, i32, vp], None),
             "dj_cpp_partition_cols": ([vp, i32, i64, vp, i32, i32, i32, u32, vp], vp),
+            "dj_cpp_distributed_inner_join_ncols_multi": ([vp, vp, i32, i64, vp, i32, i64,
+                                                           vp, vp, i32, i32, i32], vp),
+            "dj_cpp_shuffle_on_ncols": ([vp, vp, i32, i64, vp, i32, i32, u32, i32], vp),
+            "dj_cpp_partition_ncols": ([vp, i32, i64, vp, i32, i32, i32, u32, vp], vp),
+            "dj_table_column_null_mask": ([vp, i32], vp),
+            "dj_table_column_null_count": ([vp, i32], i64),
+            "dj_gather_bitmasks": ([vp, vp, i32, vp, i64, vp, i32, vp, i32], None),
+            "dj_copy_bitmask_segments": ([vp, vp, vp, i32, vp], i64),
         }
         for name, (argtypes, restype) in sigs.items():
             f = getattr(_lib, name)
@@ -526,6 +534,191 @@ def cpp_shuffle_on(comm, d_keys, d_pay, n, hash_fn=HASH_MURMUR3, seed=0,
     else:
         t = lib().dj_cpp_shuffle_on_i64(comm.ptr, d_keys.ptr, d_pay.ptr, n, hash_fn, seed)
     return table_to_numpy(t)
+
+
+# ------------------------------------------------- nullable columns (masks)
+
+class NColDesc(ctypes.Structure):
+    _fields_ = [("type_id", ctypes.c_int), ("data", ctypes.c_void_p),
+                ("chars", ctypes.c_void_p), ("chars_bytes", ctypes.c_int64),
+                ("null_mask", ctypes.c_void_p), ("null_count", ctypes.c_int64)]
+
+
+def pack_mask(valid):
+    """bool array -> uint32 mask words in the cuDF layout (row i = bit i % 32,
+    LSB first, of word i / 32), padded with 0 bits to a multiple of 64 rows."""
+    valid = np.asarray(valid, dtype=bool)
+    padded = np.zeros((len(valid) + 63) // 64 * 64, dtype=bool)
+    padded[:len(valid)] = valid
+    return np.packbits(padded, bitorder="little").view(np.uint32)
+
+
+def unpack_mask(words, n):
+    """uint32 mask words -> bool array of the first n rows."""
+    bits = np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little")
+    return bits[:n].astype(bool)
+
+
+class DeviceMask:
+    """Owning device validity mask; `.ptr` is the mask pointer and
+    `.null_count` the number of False rows of the uploaded bool array."""
+
+    def __init__(self, valid):
+        valid = np.asarray(valid, dtype=bool)
+        self.n = len(valid)
+        self.null_count = int(self.n - valid.sum())
+        words = pack_mask(valid)
+        self.ptr = lib().dj_dmalloc(max(words.nbytes, 64))
+        if words.nbytes:
+            lib().dj_memcpy_h2d(self.ptr, words.ctypes.data, words.nbytes)
+
+    def free(self):
+        if self.ptr:
+            lib().dj_dfree(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def upload_mask(bool_array):
+    """Upload a bool array (True = valid) as a validity mask; returns a
+    DeviceMask to name as the `mask` of a nullable column descriptor."""
+    return DeviceMask(bool_array)
+
+
+def _pack_ncols(cols):
+    """cols: (type_id, data_ptr[, chars_ptr, chars_bytes]) tuples, each with an
+    optional trailing DeviceMask (or None) -> NColDesc array."""
+    arr = (NColDesc * max(len(cols), 1))()
+    for i, c in enumerate(cols):
+        c = tuple(c)
+        mask = None
+        if c and (c[-1] is None or isinstance(c[-1], DeviceMask)) and len(c) in (3, 5):
+            mask, c = c[-1], c[:-1]
+        arr[i].type_id = c[0]
+        arr[i].data = c[1]
+        arr[i].chars = c[2] if len(c) > 2 else None
+        arr[i].chars_bytes = c[3] if len(c) > 3 else 0
+        arr[i].null_mask = mask.ptr if mask is not None else None
+        arr[i].null_count = mask.null_count if mask is not None else 0
+    return arr
+
+
+def table_to_numpy_nullable(tbl_ptr):
+    """table_to_numpy plus validity: returns (cols, masks), masks[c] a bool
+    array of the n rows (True = valid) or None when column c has no mask.
+    Checks each column's null count against its mask. Frees the table."""
+    L = lib()
+    n = L.dj_table_num_rows(tbl_ptr)
+    masks = []
+    for c in range(L.dj_table_num_columns(tbl_ptr)):
+        m = L.dj_table_column_null_mask(tbl_ptr, c)
+        if not m:
+            masks.append(None)
+            continue
+        words = np.zeros((n + 31) // 32, dtype=np.uint32)
+        if n:
+            L.dj_memcpy_d2h(words.ctypes.data, m, words.nbytes)
+        valid = unpack_mask(words, n)
+        count = L.dj_table_column_null_count(tbl_ptr, c)
+        if count != n - int(valid.sum()):
+            raise AssertionError(f"column {c}: null_count {count} but the mask marks "
+                                 f"{n - int(valid.sum())} of {n} rows null")
+        masks.append(valid)
+    return table_to_numpy(tbl_ptr), masks
+
+
+def cpp_distributed_inner_join_ncols_multi(comm, lcols, ln, rcols, rn, left_on, right_on,
+                                           over_decom=1):
+    """cpp_distributed_inner_join_cols_multi over nullable columns (each col
+    tuple may end in a DeviceMask). Null keys join with null == null.
+    Returns (cols, masks) as table_to_numpy_nullable."""
+    la, ra = _pack_ncols(lcols), _pack_ncols(rcols)
+    lon = np.asarray(left_on, dtype=np.int32)
+    ron = np.asarray(right_on, dtype=np.int32)
+    t = lib().dj_cpp_distributed_inner_join_ncols_multi(
+        comm.ptr, ctypes.cast(la, ctypes.c_void_p), len(lcols), ln,
+        ctypes.cast(ra, ctypes.c_void_p), len(rcols), rn,
+        lon.ctypes.data, ron.ctypes.data, len(lon), over_decom, 0)
+    return table_to_numpy_nullable(t)
+
+
+def cpp_shuffle_on_ncols(comm, cols, n, on, hash_fn=HASH_MURMUR3, seed=0, compression=False):
+    """cpp_shuffle_on_cols over nullable columns; returns (cols, masks)."""
+    arr = _pack_ncols(cols)
+    keys = np.asarray(on, dtype=np.int32)
+    t = lib().dj_cpp_shuffle_on_ncols(comm.ptr, ctypes.cast(arr, ctypes.c_void_p), len(cols), n,
+                                      keys.ctypes.data, len(keys), hash_fn, seed,
+                                      int(bool(compression)))
+    return table_to_numpy_nullable(t)
+
+
+def cpp_partition_ncols(cols, n, on, nparts, hash_fn=HASH_MURMUR3, seed=0):
+    """cpp_partition_cols over nullable columns; returns
+    ((cols, masks), host offsets[nparts+1])."""
+    arr = _pack_ncols(cols)
+    keys = np.asarray(on, dtype=np.int32)
+    offsets = np.zeros(nparts + 1, dtype=np.int64)
+    t = lib().dj_cpp_partition_ncols(ctypes.cast(arr, ctypes.c_void_p), len(cols), n,
+                                     keys.ctypes.data, len(keys), nparts, hash_fn, seed,
+                                     offsets.ctypes.data)
+    return table_to_numpy_nullable(t), offsets
+
+
+def gather_bitmasks(src_masks, d_idx_ptr, n, reps=1, cols_per_launch=0):
+    """The mask gather kernel through its test/bench hook. src_masks: device
+    mask pointers (or None = all valid), one per column; cols_per_launch
+    columns go into one kernel launch (0 = the engine's choice). Returns
+    (list of bool[n] arrays, int64 null counts, per-repetition ms, raw words
+    per column — roundup(n, 64) / 32 of them, to check the zeroed tail)."""
+    L = lib()
+    nc = len(src_masks)
+    nbytes = (n + 63) // 64 * 8
+    dsts = [L.dj_dmalloc(max(nbytes, 8)) for _ in range(nc)]
+    src = (ctypes.c_void_p * max(nc, 1))(*[m if m else None for m in src_masks])
+    dst = (ctypes.c_void_p * max(nc, 1))(*dsts)
+    counts = np.zeros(max(nc, 1), dtype=np.int64)
+    ms = np.zeros(max(reps, 1), dtype=np.float64)
+    L.dj_gather_bitmasks(ctypes.cast(src, ctypes.c_void_p), ctypes.cast(dst, ctypes.c_void_p),
+                         nc, d_idx_ptr, n, counts.ctypes.data, reps, ms.ctypes.data,
+                         cols_per_launch)
+    outs, raws = [], []
+    for d in dsts:
+        words = np.zeros(nbytes // 4, dtype=np.uint32)
+        if nbytes:
+            L.dj_memcpy_d2h(words.ctypes.data, d, nbytes)
+        L.dj_dfree(d)
+        raws.append(words)
+        outs.append(unpack_mask(words, n))
+    return outs, counts[:nc], ms, raws
+
+
+def copy_bitmask_segments(segments, fill=0xFFFFFFFF):
+    """The mask segment copy kernel through its test hook. segments:
+    (device mask pointer or None, first source bit, number of bits) tuples
+    landing back to back. Returns (uint32 destination words — ceil(total/32)
+    of them, bool[total], unset-bit count from the null-count kernel)."""
+    L = lib()
+    S = len(segments)
+    src = (ctypes.c_void_p * max(S, 1))(*[s[0] if s[0] else None for s in segments])
+    sbit = np.asarray([s[1] for s in segments] or [0], dtype=np.int64)
+    nbits = np.asarray([s[2] for s in segments] or [0], dtype=np.int64)
+    total = int(sum(s[2] for s in segments))
+    nwords = (total + 31) // 32
+    words = np.full(nwords + 2, fill, dtype=np.uint32)  # two guard words behind
+    d = L.dj_dmalloc(words.nbytes)
+    L.dj_memcpy_h2d(d, words.ctypes.data, words.nbytes)
+    nulls = L.dj_copy_bitmask_segments(ctypes.cast(src, ctypes.c_void_p), sbit.ctypes.data,
+                                       nbits.ctypes.data, S, d)
+    L.dj_memcpy_d2h(words.ctypes.data, d, words.nbytes)
+    L.dj_dfree(d)
+    if not (words[nwords:] == np.uint32(fill)).all():
+        raise AssertionError("copy_bitmask_segments wrote past its last destination word")
+    return words[:nwords], unpack_mask(words[:nwords], total), int(nulls)
 
 
 GATHER_FUSED, GATHER_PER_COLUMN, GATHER_AUTO = 0, 1, 2

@@ -31,6 +31,7 @@
 #include <iostream>
 #include <map>
 #include <mutex>
+#include <string>
 #include <unordered_map>
 #include <vector>
 
@@ -178,6 +179,37 @@ void sync_streams()
   DJ_HIP_CALL(hipStreamSynchronize(dj_rt_comm_stream()));
 }
 
+/* one source range of dj::copy_bitmask_segments: nbits bits of `src` (nullptr
+ * = all valid) from bit src_bit on; destination ranges follow one another */
+struct BitSeg {
+  const uint32_t* src;
+  int64_t src_bit;
+  int64_t nbits;
+};
+
+/* dst bits [0, sum nbits) = the segments back to back, on `st`. Returns the
+ * device segment table, which must outlive the kernel: keep it until the
+ * stream has been synchronized. */
+DBuf copy_bit_segments(std::vector<BitSeg> const& segs, uint32_t* dst, hipStream_t st)
+{
+  const size_t S = segs.size();
+  std::vector<int64_t> blk(3 * S + 1);
+  int64_t total = 0;
+  for (size_t i = 0; i < S; i++) {
+    blk[i] = (int64_t)(uintptr_t)segs[i].src;
+    blk[S + i] = segs[i].src_bit;
+    blk[2 * S + i] = total;
+    total += segs[i].nbits;
+  }
+  blk[3 * S] = total;
+  DBuf d(blk.size() * 8);
+  if (total > 0) {
+    DJ_HIP_CALL(hipMemcpy(d.p, blk.data(), blk.size() * 8, hipMemcpyHostToDevice));
+    dj::copy_bitmask_segments(d.p, (int)S, total, dst, st);
+  }
+  return d;
+}
+
 /* int64 view of a key column (widening INT32; spec: dj_hash.h operates on
  * int64 keys — INT32 keys are widened, identity placement k % G preserved) */
 /* fused multi-column key: h_i = chain of mix64 over the key tuple — the
@@ -188,19 +220,43 @@ void sync_streams()
 __global__ void fuse_keys_kernel(const int64_t* __restrict__ c0, const int64_t* __restrict__ c1,
                                  const int64_t* __restrict__ c2, const int64_t* __restrict__ c3,
                                  uint32_t kinds /*4 bits per col: dj::kKey* */, int ncols,
-                                 int64_t n, int weak, int64_t* __restrict__ out)
+                                 int64_t n, int weak, int64_t* __restrict__ out,
+                                 const uint32_t* __restrict__ m0 = nullptr,
+                                 const uint32_t* __restrict__ m1 = nullptr,
+                                 const uint32_t* __restrict__ m2 = nullptr,
+                                 const uint32_t* __restrict__ m3 = nullptr)
 {
   const int64_t* cols[4] = {c0, c1, c2, c3};
+  const uint32_t* masks[4] = {m0, m1, m2, m3};
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
     uint64_t h = 0x9e3779b97f4a7c15ull;
     for (int c = 0; c < ncols; c++) {
-      int64_t v = dj::load_key_i64(cols[c], (int)((kinds >> (4 * c)) & 0xF), i);
+      /* a null element enters the chain as the null element hash; the value
+       * stored under it is not read */
+      int64_t v = dj::key_is_valid(masks[c], i)
+                    ? dj::load_key_i64(cols[c], (int)((kinds >> (4 * c)) & 0xF), i)
+                    : (int64_t)dj::kNullKeyHash;
       h = dj_mix64(h ^ (uint64_t)v);
     }
     out[i] = weak ? (int64_t)(h & 0xF) : (int64_t)h;
   }
+}
+
+/* placement hash of a single nullable integer-rep key column: dj_row_hash of
+ * a valid element, the null element hash of a null one (never reading the
+ * value under it) */
+__global__ void nullable_key_hash_kernel(const void* __restrict__ src, int kind,
+                                         const uint32_t* __restrict__ valid, int64_t n,
+                                         int hash_fn, uint32_t seed, int64_t* __restrict__ out)
+{
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride)
+    out[i] = dj::key_is_valid(valid, i)
+               ? (int64_t)dj_row_hash(dj::load_key_i64(src, kind, i), hash_fn, seed)
+               : (int64_t)dj::kNullKeyHash;
 }
 
 bool is_string(cudf::column_view col) { return col.type().id() == cudf::type_id::STRING; }
@@ -241,6 +297,38 @@ void check_key_pairs(cudf::table_view left, cudf::table_view right,
   }
 }
 
+bool any_nullable(cudf::table_view t)
+{
+  for (cudf::size_type c = 0; c < t.num_columns(); c++)
+    if (t.column(c).nullable()) return true;
+  return false;
+}
+
+bool any_nullable_key(cudf::table_view t, std::vector<cudf::size_type> const& on)
+{
+  for (auto c : on)
+    if (t.column(c).nullable()) return true;
+  return false;
+}
+
+/* bit c set: column c carries a validity mask (columns 0..31: callers refuse
+ * a wider table that has any mask, see the AllToAllCommunicator constructor) */
+uint32_t nullable_bits(cudf::table_view t)
+{
+  uint32_t bits = 0;
+  for (cudf::size_type c = 0; c < t.num_columns() && c < 32; c++)
+    if (t.column(c).nullable()) bits |= 1u << c;
+  return bits;
+}
+
+void check_no_masks(cudf::table_view t, const char* what)
+{
+  if (any_nullable(t))
+    throw std::runtime_error(std::string(what) +
+                             ": nullable columns (validity masks) are not supported here; "
+                             "use shuffle_on / distributed_inner_join / AllToAllCommunicator");
+}
+
 bool any_string_key(cudf::table_view t, std::vector<cudf::size_type> const& on)
 {
   for (auto c : on)
@@ -257,11 +345,15 @@ DBuf fuse_keys(cudf::table_view t, std::vector<cudf::size_type> const& on, hipSt
   DJ_CHECK_ERROR(on.size() >= 1 && on.size() <= 4,
                  "multi-column join keys: 1..4 key columns supported");
   const int64_t* ptrs[4] = {nullptr, nullptr, nullptr, nullptr};
+  const uint32_t* masks[4] = {nullptr, nullptr, nullptr, nullptr};
   uint32_t kinds = 0;
   std::vector<DBuf> str_keys;
   for (size_t c = 0; c < on.size(); c++) {
     cudf::column_view col = t.column(on[c]);
+    masks[c] = col.null_mask();
     if (is_string(col)) {
+      /* rows are hashed whatever their validity; the kernel below replaces
+       * the hash of a null row by the null constant */
       str_keys.emplace_back((size_t)(n > 0 ? n : 1) * 8);
       dj::hash_strings(col.head<int32_t>(), (const uint8_t*)col.chars(), n,
                        (uint64_t*)str_keys.back().p, st);
@@ -276,7 +368,8 @@ DBuf fuse_keys(cudf::table_view t, std::vector<cudf::size_type> const& on, hipSt
   DBuf out((size_t)(n > 0 ? n : 1) * 8);
   if (n > 0) {
     hipLaunchKernelGGL(fuse_keys_kernel, dim3(grid_for_n(n)), dim3(kBlock), 0, st, ptrs[0],
-                       ptrs[1], ptrs[2], ptrs[3], kinds, (int)on.size(), n, weak, out.i64());
+                       ptrs[1], ptrs[2], ptrs[3], kinds, (int)on.size(), n, weak, out.i64(),
+                       masks[0], masks[1], masks[2], masks[3]);
     DJ_HIP_CALL(hipGetLastError());
     /* the row-hash temporaries go back to the pool on return */
     if (!str_keys.empty()) DJ_HIP_CALL(hipStreamSynchronize(st));
@@ -311,12 +404,14 @@ cudf::table_view view_i64_pair(const void* c0, const void* c1, int64_t n)
                            cudf::column_view(i64, (cudf::size_type)n, c1)});
 }
 
-/* the hot shape: exactly two INT64 columns, one of them the key */
+/* the hot shape: exactly two INT64 columns, one of them the key, and no
+ * validity mask (a table with any mask takes the general paths) */
 bool is_i64_pair(cudf::table_view t, cudf::size_type key_col)
 {
   return t.num_columns() == 2 && (key_col == 0 || key_col == 1) &&
          t.column(0).type().id() == cudf::type_id::INT64 &&
-         t.column(1).type().id() == cudf::type_id::INT64;
+         t.column(1).type().id() == cudf::type_id::INT64 && !t.column(0).nullable() &&
+         !t.column(1).nullable();
 }
 
 /* both sides of a join have it with the key in front: the engine's four
@@ -426,12 +521,20 @@ column::column(size_type size, int64_t chars_bytes)
 }
 
 column::column(column&& o) noexcept
-  : _type(o._type), _size(o._size), _data(o._data), _chars(o._chars), _chars_size(o._chars_size)
+  : _type(o._type),
+    _size(o._size),
+    _data(o._data),
+    _chars(o._chars),
+    _chars_size(o._chars_size),
+    _null_mask(o._null_mask),
+    _null_count(o._null_count)
 {
   o._data = nullptr;
   o._chars = nullptr;
   o._size = 0;
   o._chars_size = 0;
+  o._null_mask = nullptr;
+  o._null_count = 0;
 }
 
 column& column::operator=(column&& o) noexcept
@@ -439,15 +542,20 @@ column& column::operator=(column&& o) noexcept
   if (this != &o) {
     if (_data) pool_free(_data);
     if (_chars) pool_free(_chars);
+    if (_null_mask) pool_free(_null_mask);
     _type = o._type;
     _size = o._size;
     _data = o._data;
     _chars = o._chars;
     _chars_size = o._chars_size;
+    _null_mask = o._null_mask;
+    _null_count = o._null_count;
     o._data = nullptr;
     o._chars = nullptr;
     o._size = 0;
     o._chars_size = 0;
+    o._null_mask = nullptr;
+    o._null_count = 0;
   }
   return *this;
 }
@@ -456,6 +564,36 @@ column::~column()
 {
   if (_data) pool_free(_data);
   if (_chars) pool_free(_chars);
+  if (_null_mask) pool_free(_null_mask);
+}
+
+void column::set_null_mask(void* adopt, size_type null_count)
+{
+  if (_null_mask && _null_mask != adopt) pool_free(_null_mask);
+  _null_mask = (bitmask_type*)adopt;
+  _null_count = adopt ? null_count : 0;
+}
+
+bitmask_type* column::allocate_null_mask()
+{
+  /* never empty, so that a 0-row column can still be nullable() */
+  set_null_mask(pool_alloc(std::max<size_t>(bitmask_allocation_size_bytes(_size), 64)),
+                UNKNOWN_NULL_COUNT);
+  return _null_mask;
+}
+
+size_type column::null_count() const
+{
+  if (_null_count != UNKNOWN_NULL_COUNT) return _null_count;
+  if (_null_mask == nullptr || _size == 0) return _null_count = 0;
+  hipStream_t st = dj_rt_stream();
+  DBuf cnt(8);
+  DJ_HIP_CALL(hipMemsetAsync(cnt.p, 0, 8, st));
+  dj::count_unset_bits(_null_mask, _size, (unsigned long long*)cnt.p, st);
+  unsigned long long h = 0;
+  DJ_HIP_CALL(hipMemcpyAsync(&h, cnt.p, 8, hipMemcpyDeviceToHost, st));
+  DJ_HIP_CALL(hipStreamSynchronize(st));
+  return _null_count = (size_type)h;
 }
 
 }  // namespace cudf
@@ -765,17 +903,33 @@ CommunicationGroup::CommunicationGroup(int grid_size_, int stride_, int mpi_rank
 
 /* ------------------------------------------------------- communicate_sizes */
 
-void communicate_sizes(std::vector<int64_t> const& send_offset,
-                       std::vector<int64_t>& recv_offset,
-                       CommunicationGroup comm_group,
-                       Communicator* communicator)
+namespace {
+
+/* communicate_sizes, optionally carrying `extra` (33 bits) above bit 30 of
+ * every count: the internal exchange of AllToAllCommunicator, whose counts
+ * are size_type rows, agrees on column nullability this way without a
+ * message of its own. peer_extra (G entries) receives every rank's word. */
+void exchange_sizes(std::vector<int64_t> const& send_offset, std::vector<int64_t>& recv_offset,
+                    CommunicationGroup comm_group, Communicator* communicator, bool fold,
+                    uint64_t extra, std::vector<uint64_t>* peer_extra)
 {
   const int G = comm_group.size();
   const int me = comm_group.get_local_idx();
   std::vector<int64_t> send_counts(G);
-  for (int i = 0; i < G; i++) send_counts[i] = send_offset[i + 1] - send_offset[i];
+  for (int i = 0; i < G; i++) {
+    send_counts[i] = send_offset[i + 1] - send_offset[i];
+    if (fold) {
+      DJ_CHECK_ERROR(send_counts[i] >= 0 && send_counts[i] <= (int64_t)INT32_MAX,
+                     "all-to-all: a slice's row count exceeds size_type");
+      if (i != me) send_counts[i] |= (int64_t)(extra << 31);
+    }
+  }
   std::vector<int64_t> recv_counts(G, 0);
   recv_counts[me] = send_counts[me];
+  if (peer_extra) {
+    peer_extra->assign(G, 0);
+    (*peer_extra)[me] = extra;
+  }
   if (G > 1) {
     /* counts move through the communicator via a small device staging
      * buffer (the reference kept them on MPI host buffers,
@@ -796,12 +950,25 @@ void communicate_sizes(std::vector<int64_t> const& send_offset,
     DJ_HIP_CALL(hipMemcpyAsync(got.data(), d_recv.p, (size_t)G * 8, hipMemcpyDeviceToHost,
                                dj_rt_comm_stream()));
     DJ_HIP_CALL(hipStreamSynchronize(dj_rt_comm_stream()));
-    for (int i = 0; i < G; i++)
-      if (i != me) recv_counts[i] = got[i];
+    for (int i = 0; i < G; i++) {
+      if (i == me) continue;
+      recv_counts[i] = fold ? (got[i] & (int64_t)0x7FFFFFFF) : got[i];
+      if (fold && peer_extra) (*peer_extra)[i] = (uint64_t)got[i] >> 31;
+    }
   }
   recv_offset.resize(G + 1);
   recv_offset[0] = 0;
   for (int i = 0; i < G; i++) recv_offset[i + 1] = recv_offset[i] + recv_counts[i];
+}
+
+}  // namespace
+
+void communicate_sizes(std::vector<int64_t> const& send_offset,
+                       std::vector<int64_t>& recv_offset,
+                       CommunicationGroup comm_group,
+                       Communicator* communicator)
+{
+  exchange_sizes(send_offset, recv_offset, comm_group, communicator, false, 0, nullptr);
 }
 
 void communicate_sizes(std::vector<cudf::size_type> const& send_offset,
@@ -840,6 +1007,7 @@ void append_to_all_to_all_comm_buffers(cudf::table_view input,
                                        std::vector<ColumnCompressionOptions> compression_options)
 {
   check_no_compression(compression_options);
+  check_no_masks(input, "append_to_all_to_all_comm_buffers");
   for (cudf::size_type c = 0; c < input.num_columns(); c++) {
     DJ_CHECK_ERROR(cudf::size_of(input.column(c).type()) > 0,
                    "all-to-all: fixed-width columns only through the generic plan API");
@@ -922,6 +1090,19 @@ AllToAllCommunicator::AllToAllCommunicator(
   Communicator* communicator_,
   std::vector<ColumnCompressionOptions> compression_options_,
   bool explicit_copy_to_current_rank_)
+  : AllToAllCommunicator(input_table_, std::move(offsets), comm_group_, communicator_,
+                         std::move(compression_options_), explicit_copy_to_current_rank_, 0u)
+{
+}
+
+AllToAllCommunicator::AllToAllCommunicator(
+  cudf::table_view input_table_,
+  std::vector<cudf::size_type> offsets,
+  CommunicationGroup comm_group_,
+  Communicator* communicator_,
+  std::vector<ColumnCompressionOptions> compression_options_,
+  bool explicit_copy_to_current_rank_,
+  uint32_t route_tag)
   : input_table(input_table_),
     comm_group(comm_group_),
     communicator(communicator_),
@@ -932,7 +1113,33 @@ AllToAllCommunicator::AllToAllCommunicator(
   validate_compression(input_table, compression_options);
   DJ_CHECK_ERROR((int)send_offsets.size() == comm_group.size() + 1,
                  "AllToAllCommunicator: offsets must have comm_group.size()+1 entries");
-  communicate_sizes(send_offsets, recv_offsets, comm_group, communicator);
+  /* row counts, with this rank's per-column nullability (and the caller's
+   * route tag) folded above them: the ranks must agree on which columns ship
+   * a mask, or the slice sizes of the exchange would not pair up. A column
+   * is shipped with a mask when it has one on ANY rank of the group; a rank
+   * whose column has none sends all-valid slices. */
+  {
+    const int ncols = input_table.num_columns();
+    DJ_CHECK_ERROR(!any_nullable(input_table) || ncols <= dj::kMaxSchemaCols,
+                   "all-to-all: nullable columns need a table of at most 32 columns");
+    const uint32_t my_bits = nullable_bits(input_table);
+    DJ_CHECK_ERROR(!(route_tag & 2u) || ncols < 32, "all-to-all: route tag needs a free bit");
+    const uint64_t extra = (uint64_t)(route_tag & 1u) | ((uint64_t)my_bits << 1) |
+                           ((uint64_t)((route_tag >> 1) & 1u) << 32);
+    std::vector<int64_t> wide(send_offsets.begin(), send_offsets.end());
+    std::vector<uint64_t> peers;
+    exchange_sizes(wide, recv_offsets, comm_group, communicator, true, extra, &peers);
+    const uint32_t col_bits = ncols >= 32 ? 0xFFFFFFFFu : ((1u << ncols) - 1u);
+    for (uint64_t e : peers) {
+      nullable_cols |= (uint32_t)(e >> 1) & col_bits;
+      const uint32_t tag = (uint32_t)(e & 1u) | (ncols < 32 ? (uint32_t)((e >> 32) & 1u) << 1 : 0u);
+      DJ_CHECK_ERROR(tag == route_tag,
+                     "all-to-all: the ranks of the group passed different route tags. In "
+                     "distributed_inner_join this means they disagree on whether a key column "
+                     "(or a column of a 2 x INT64 table) is nullable, which selects the join "
+                     "route; pass a mask (all valid) for that column on every rank");
+    }
+  }
 
   /* strings columns: exchange per-peer char byte counts; precompute the row
    * sizes to send (gather_string_offsets + calculate_string_sizes_from_offsets
@@ -1016,6 +1223,8 @@ std::unique_ptr<cudf::table> AllToAllCommunicator::allocate_communicated_table()
         nrows, strings->recv_char_offsets[c].back()));
     else
       cols.push_back(std::make_unique<cudf::column>(input_table.column(c).type(), nrows));
+    /* filled by launch_communication's merge, self slice included */
+    if ((nullable_cols >> c) & 1u) cols.back()->allocate_null_mask();
   }
   auto out = std::make_unique<cudf::table>(std::move(cols));
   if (explicit_copy_to_current_rank) {
@@ -1135,6 +1344,49 @@ void AllToAllCommunicator::launch_communication(cudf::mutable_table_view communi
                  &recv_offsets, compression_options[c]);
     }
   }
+
+  /* validity masks of the columns nullable anywhere in the group: each
+   * peer's row slice is cut out of the column's mask into a word-aligned
+   * packed slice of one staging buffer (dj::copy_bitmask_segments) and
+   * travels raw, as uint32 words, behind the data buffers; the receiver
+   * merges the G slices at recv_offsets below. Never compressed. The self
+   * slice does not travel: the merge reads it from the input mask. */
+  struct MaskWire {
+    cudf::size_type col;
+    DBuf send_stage, recv_stage;
+    std::vector<int64_t> swo, rwo;  // word offsets per peer (G+1), self empty
+  };
+  std::vector<MaskWire> mwires;
+  std::vector<DBuf> seg_tables;
+  mwires.reserve((size_t)input_table.num_columns());
+  for (cudf::size_type c = 0; c < input_table.num_columns() && nullable_cols; c++) {
+    if (!((nullable_cols >> c) & 1u)) continue;
+    DJ_CHECK_ERROR(communicated_table.column(c).null_mask() != nullptr,
+                   "launch_communication: the communicated table lacks the mask of a nullable "
+                   "column (allocate it with allocate_communicated_table)");
+    mwires.emplace_back();
+    MaskWire& w = mwires.back();
+    w.col = c;
+    w.swo.assign(G + 1, 0);
+    w.rwo.assign(G + 1, 0);
+    std::vector<BitSeg> segs;
+    const uint32_t* mask = input_table.column(c).null_mask();
+    for (int i = 0; i < G; i++) {
+      const int64_t scount = i == me ? 0 : soff[i + 1] - soff[i];
+      const int64_t rcount = i == me ? 0 : recv_offsets[i + 1] - recv_offsets[i];
+      const int64_t swords = (scount + 31) / 32;
+      w.swo[i + 1] = w.swo[i] + swords;
+      w.rwo[i + 1] = w.rwo[i] + (rcount + 31) / 32;
+      segs.push_back(BitSeg{mask, soff[i], scount});
+      segs.push_back(BitSeg{nullptr, 0, swords * 32 - scount});  // pad to the word
+    }
+    w.send_stage = DBuf((size_t)std::max<int64_t>(w.swo[G], 1) * 4);
+    w.recv_stage = DBuf((size_t)std::max<int64_t>(w.rwo[G], 1) * 4);
+    seg_tables.push_back(copy_bit_segments(segs, (uint32_t*)w.send_stage.p, st));
+    plains.push_back(Plain{(const int8_t*)w.send_stage.p, (int8_t*)w.recv_stage.p, 4, &w.swo,
+                           &w.rwo});
+  }
+  if (!mwires.empty()) DJ_HIP_CALL(hipStreamSynchronize(st));
 
   /* compress send slices (compute stream), then read final sizes */
   int64_t max_recv_count = 0;
@@ -1259,6 +1511,23 @@ void AllToAllCommunicator::launch_communication(cudf::mutable_table_view communi
   }
   (void)preallocated_pinned_buffer;
 
+  /* receiver-side: merge the received mask slices, and this rank's own
+   * slice, into the column's mask at recv_offsets; the column counts its
+   * nulls when next asked (its mutable view forgot the count) */
+  for (auto& w : mwires) {
+    std::vector<BitSeg> segs;
+    for (int i = 0; i < G; i++) {
+      const int64_t rcount = recv_offsets[i + 1] - recv_offsets[i];
+      if (i == me)
+        segs.push_back(BitSeg{input_table.column(w.col).null_mask(), soff[me], rcount});
+      else
+        segs.push_back(BitSeg{(const uint32_t*)w.recv_stage.p + w.rwo[i], 0, rcount});
+    }
+    seg_tables.push_back(
+      copy_bit_segments(segs, communicated_table.column(w.col).null_mask(), st));
+  }
+  if (!mwires.empty()) DJ_HIP_CALL(hipStreamSynchronize(st));
+
   /* receiver-side: rebuild string offsets from the received sizes by scan
    * with offset[0]=0 (strings_column.cu:111-131) */
   if (strings) {
@@ -1330,6 +1599,7 @@ void gather_table_columns(cudf::table_view src, DBuf& idx, int64_t n, cudf::size
   const int64_t* key_src = nullptr;
   void* key_dst = nullptr;
   int key_width = 0;
+  const size_t first = cols.size();
   for (cudf::size_type c = 0; c < src.num_columns(); c++) {
     cudf::column_view v = src.column(c);
     if (v.type().id() == cudf::type_id::STRING) {
@@ -1360,6 +1630,37 @@ void gather_table_columns(cudf::table_view src, DBuf& idx, int64_t n, cudf::size
     hipLaunchKernelGGL(narrow_key_kernel, dim3(grid_for_n(n)), dim3(kBlock), 0, st, key_src, n,
                        key_width, key_dst);
   dj::gather_table(gc.data(), (int)gc.size(), idx.i64(), n, dj::kGatherAuto, st);
+
+  /* validity: every nullable source column gets an output mask through
+   * dj::gather_bitmasks over the same index array (launches of their own,
+   * one per column, after the value gather — DESIGN.md §3d), key and STRING
+   * columns included; a mask-free table stops here */
+  if (!any_nullable(src)) return;
+  std::vector<cudf::column*> masked;
+  std::vector<const uint32_t*> msrc;
+  for (cudf::size_type c = 0; c < src.num_columns(); c++) {
+    if (!src.column(c).nullable()) continue;
+    masked.push_back(cols[first + (size_t)c].get());
+    msrc.push_back(src.column(c).null_mask());
+  }
+  /* any number of nullable columns: descriptors of at most kMaxSchemaCols,
+   * as gather_table takes its columns */
+  const size_t nm = masked.size();
+  DBuf d_counts(nm * 4);
+  DJ_HIP_CALL(hipMemsetAsync(d_counts.p, 0, nm * 4, st));
+  for (size_t k0 = 0; k0 < nm; k0 += dj::kMaxSchemaCols) {
+    dj::BitmaskGatherDesc bd{};
+    bd.ncols = (int)std::min<size_t>(nm - k0, dj::kMaxSchemaCols);
+    for (int k = 0; k < bd.ncols; k++) {
+      bd.src[k] = msrc[k0 + (size_t)k];
+      bd.dst[k] = masked[k0 + (size_t)k]->allocate_null_mask();
+    }
+    dj::gather_bitmasks(bd, idx.i64(), n, (uint32_t*)d_counts.p + k0, st);
+  }
+  std::vector<uint32_t> h_counts(nm);
+  DJ_HIP_CALL(hipMemcpyAsync(h_counts.data(), d_counts.p, nm * 4, hipMemcpyDeviceToHost, st));
+  DJ_HIP_CALL(hipStreamSynchronize(st));
+  for (size_t k = 0; k < nm; k++) masked[k]->set_null_count((cudf::size_type)h_counts[k]);
 }
 
 /* stable hash-partition of an arbitrary table into nparts contiguous ranges:
@@ -1442,6 +1743,19 @@ PartitionedTable place_rows(cudf::table_view input, std::vector<cudf::size_type>
     DJ_CHECK_ERROR(hash_fn != DJ_HASH_IDENTITY,
                    "identity-hash shuffle requires a single key column");
     fused = fuse_keys(input, on, dj_rt_stream());
+  } else if (input.column(on[0]).nullable()) {
+    /* a single nullable integer key: valid rows place exactly as without the
+     * mask, null rows on the null element hash (dj_hash.h). The per-row hash
+     * is computed here and the partition runs on it with the identity hash
+     * (hash % nparts either way), leaving the partition kernels untouched. */
+    const int64_t n = input.num_rows();
+    cudf::column_view col = input.column(on[0]);
+    fused = DBuf((size_t)(n > 0 ? n : 1) * 8);
+    if (n > 0)
+      hipLaunchKernelGGL(nullable_key_hash_kernel, dim3(grid_for_n(n)), dim3(kBlock), 0,
+                         dj_rt_stream(), col.head<void>(), key_kind(col.type()),
+                         col.null_mask(), n, hash_fn, seed, fused.i64());
+    return partition_table(input, on[0], nparts, DJ_HASH_IDENTITY, 0, fused.i64());
   }
   return partition_table(input, on[0], nparts, hash_fn, seed, fused.p ? fused.i64() : nullptr);
 }
@@ -1515,6 +1829,10 @@ std::unique_ptr<cudf::table> empty_join_result(cudf::table_view left, cudf::tabl
         cols.push_back(std::make_unique<cudf::column>((cudf::size_type)0, (int64_t)0));
       else
         cols.push_back(std::make_unique<cudf::column>(t.column(c).type(), (cudf::size_type)0));
+      if (t.column(c).nullable()) {
+        cols.back()->allocate_null_mask();
+        cols.back()->set_null_count(0);
+      }
     }
   return std::make_unique<cudf::table>(std::move(cols));
 }
@@ -1556,6 +1874,7 @@ dj::TupleKeyCol tuple_key_col(cudf::column_view col)
   d.data = col.head<void>();
   d.chars = (const uint8_t*)col.chars();
   d.kind = is_string(col) ? (int)dj::kKeyStr : key_kind(col.type());
+  d.valid = col.null_mask();
   return d;
 }
 
@@ -1579,7 +1898,11 @@ std::unique_ptr<cudf::table> local_inner_join(cudf::table_view left, cudf::table
     DJ_CHECK_ERROR(ls == rs, "a STRING key column must pair with a STRING key column");
     str_keys |= ls;
   }
-  const bool fused = lon.size() > 1 || str_keys;
+  /* nullable keys take the fused route too: fuse_keys gives every null
+   * element one constant, so all-null tuples meet in the bucket join, and the
+   * tuple filter applies null_equality::EQUAL against the masks */
+  const bool fused = lon.size() > 1 || str_keys || any_nullable_key(left, lon) ||
+                     any_nullable_key(right, ron);
   hipStream_t st = dj_rt_stream();
   const int64_t ln = left.num_rows(), rn = right.num_rows();
   if (ln == 0 || rn == 0) return empty_join_result(left, right);  // distributed_join.cpp:76-83
@@ -1651,6 +1974,22 @@ std::unique_ptr<cudf::table> concat_tables(std::vector<std::unique_ptr<cudf::tab
   int64_t total = 0;
   for (auto& p : parts) total += p->num_rows();
   std::vector<std::unique_ptr<cudf::column>> cols;
+  /* validity: the parts' masks back to back (a part without one counts as
+   * all valid); the segment tables live until the sync below */
+  std::vector<DBuf> seg_tables;
+  auto concat_masks = [&](cudf::size_type c, cudf::column& col) {
+    bool any = false;
+    for (auto& p : parts) any |= p->get_column(c).nullable();
+    if (!any) return;
+    std::vector<BitSeg> segs;
+    int64_t nulls = 0;
+    for (auto& p : parts) {
+      segs.push_back(BitSeg{p->get_column(c).null_mask(), 0, p->num_rows()});
+      nulls += p->get_column(c).null_count();
+    }
+    seg_tables.push_back(copy_bit_segments(segs, col.allocate_null_mask(), st));
+    col.set_null_count((cudf::size_type)nulls);
+  };
   for (cudf::size_type c = 0; c < parts[0]->num_columns(); c++) {
     auto type = parts[0]->get_column(c).type();
     if (type.id() == cudf::type_id::STRING) {
@@ -1672,6 +2011,7 @@ std::unique_ptr<cudf::table> concat_tables(std::vector<std::unique_ptr<cudf::tab
         row_off += nrows;
         char_off += nchars;
       }
+      concat_masks(c, *col);
       cols.push_back(std::move(col));
       continue;
     }
@@ -1686,6 +2026,7 @@ std::unique_ptr<cudf::table> concat_tables(std::vector<std::unique_ptr<cudf::tab
                                    hipMemcpyDeviceToDevice, st));
       off += nrows;
     }
+    concat_masks(c, *col);
     cols.push_back(std::move(col));
   }
   DJ_HIP_CALL(hipStreamSynchronize(st));
@@ -1748,7 +2089,43 @@ struct AllToAllCommunicatorAccess {
   {
     return a.recv_offsets;
   }
+  /* an AllToAllCommunicator whose row-count exchange carries the join's
+   * route tag (join_route_tag below) */
+  static std::unique_ptr<AllToAllCommunicator> make(
+    cudf::table_view t, std::vector<cudf::size_type> offsets, CommunicationGroup group,
+    Communicator* communicator, std::vector<ColumnCompressionOptions> const& opts,
+    bool explicit_copy, uint32_t route_tag)
+  {
+    return std::unique_ptr<AllToAllCommunicator>(new AllToAllCommunicator(
+      t, std::move(offsets), group, communicator, opts, explicit_copy, route_tag));
+  }
 };
+
+/* The route distributed_inner_join takes depends on nullability, which each
+ * rank sees only of its own tables: bit 0 = a key column is nullable (shuffle
+ * + local join on the fused key chain), bit 1 = two-column tables carrying a
+ * mask (which keeps 2 x INT64 tables off the fused wire path). Every route
+ * starts with the row-count exchange of an AllToAllCommunicator over the
+ * left table, one count per peer whatever the route, so the tag rides it and
+ * ranks that disagree stop loudly there instead of pairing mismatched
+ * messages. */
+static uint32_t join_route_tag(cudf::table_view left, cudf::table_view right,
+                               std::vector<cudf::size_type> const& lon,
+                               std::vector<cudf::size_type> const& ron)
+{
+  uint32_t tag = 0;
+  if (any_nullable_key(left, lon) || any_nullable_key(right, ron)) tag |= 1u;
+  if (left.num_columns() == 2 && right.num_columns() == 2 &&
+      (any_nullable(left) || any_nullable(right)))
+    tag |= 2u;
+  return tag;
+}
+
+static std::unique_ptr<cudf::table> shuffle_on_tagged(
+  cudf::table_view const& input, std::vector<cudf::size_type> const& on_columns,
+  CommunicationGroup comm_group, Communicator* communicator,
+  std::vector<ColumnCompressionOptions> compression_options, cudf::hash_id hash_function,
+  uint32_t hash_seed, bool report_timing, void* preallocated_pinned_buffer, uint32_t route_tag);
 
 namespace {
 
@@ -1857,10 +2234,11 @@ std::unique_ptr<cudf::table> distributed_inner_join_fused(
   /* pre-phase: exchanges + allocations */
   for (int b = 0; b < od; b++) {
     Batch& bt = batches[b];
-    bt.latoa = std::make_unique<AllToAllCommunicator>(lpart_view, slice_of(lposf, b), group,
-                                                      communicator, lopts, true);
-    bt.ratoa = std::make_unique<AllToAllCommunicator>(rpart_view, slice_of(rposf, b), group,
-                                                      communicator, ropts, true);
+    /* route tag 0: this path runs only on mask-free tables */
+    bt.latoa = AllToAllCommunicatorAccess::make(lpart_view, slice_of(lposf, b), group,
+                                                communicator, lopts, true, 0u);
+    bt.ratoa = AllToAllCommunicatorAccess::make(rpart_view, slice_of(rposf, b), group,
+                                                communicator, ropts, true, 0u);
     exchange_vecs(group, communicator, subcounts_of(lposf, b), bt.lsub_recv);
     exchange_vecs(group, communicator, subcounts_of(rposf, b), bt.rsub_recv);
     bt.lrecv = bt.latoa->allocate_communicated_table();
@@ -1982,10 +2360,6 @@ std::unique_ptr<cudf::table> distributed_inner_join(
   validate_compression(left, left_compression_options);
   validate_compression(right, right_compression_options);
   check_key_pairs(left, right, left_on, right_on);
-  /* composite keys and any STRING key join on the fused key chain */
-  const bool fused_keys = left_on.size() > 1 || any_string_key(left, left_on) ||
-                          any_string_key(right, right_on);
-
   const int world = communicator->mpi_size;
   const int nvl = get_nvl_partition_size(world, nvlink_domain_size < 1 ? 1 : nvlink_domain_size);
 
@@ -2008,18 +2382,25 @@ std::unique_ptr<cudf::table> distributed_inner_join(
   }
   if (nvl == 1) return local_inner_join(left, right, left_on, right_on);
 
+  /* composite keys, any STRING key and any nullable key join on the fused
+   * key chain; nullability is read after the inter-domain shuffle, which
+   * gives a column a mask when it had one on any rank of that group */
+  const uint32_t route_tag = join_route_tag(left, right, left_on, right_on);
+  const bool fused_keys = left_on.size() > 1 || any_string_key(left, left_on) ||
+                          any_string_key(right, right_on) || (route_tag & 1u);
+
   if (fused_keys) {
     /* multi-column keys, and STRING keys even alone, take the shuffle +
      * local-join route (placement on the fused key chain both sides,
      * collisions filtered in the local join); the batched od pipeline stays
      * single-integer-key — the hot shape the reference benchmarks */
     CommunicationGroup g2(nvl, 1, communicator->mpi_rank);
-    auto ls = shuffle_on(left, left_on, g2, communicator, left_compression_options,
-                         cudf::hash_id::HASH_MURMUR3, DJ_SEED_INTRA, report_timing,
-                         preallocated_pinned_buffer);
-    auto rs = shuffle_on(right, right_on, g2, communicator, right_compression_options,
-                         cudf::hash_id::HASH_MURMUR3, DJ_SEED_INTRA, report_timing,
-                         preallocated_pinned_buffer);
+    auto ls = shuffle_on_tagged(left, left_on, g2, communicator, left_compression_options,
+                                cudf::hash_id::HASH_MURMUR3, DJ_SEED_INTRA, report_timing,
+                                preallocated_pinned_buffer, route_tag);
+    auto rs = shuffle_on_tagged(right, right_on, g2, communicator, right_compression_options,
+                                cudf::hash_id::HASH_MURMUR3, DJ_SEED_INTRA, report_timing,
+                                preallocated_pinned_buffer, route_tag);
     return local_inner_join(ls->view(), rs->view(), left_on, right_on);
   }
 
@@ -2075,12 +2456,10 @@ std::unique_ptr<cudf::table> distributed_inner_join(
                                         lpart.offsets.begin() + b * G + G + 1);
     std::vector<cudf::size_type> rslice(rpart.offsets.begin() + b * G,
                                         rpart.offsets.begin() + b * G + G + 1);
-    bt.latoa = std::make_unique<AllToAllCommunicator>(lpart.tbl->view(), lslice, group,
-                                                      communicator, left_compression_options,
-                                                      true);
-    bt.ratoa = std::make_unique<AllToAllCommunicator>(rpart.tbl->view(), rslice, group,
-                                                      communicator, right_compression_options,
-                                                      true);
+    bt.latoa = AllToAllCommunicatorAccess::make(lpart.tbl->view(), lslice, group, communicator,
+                                                left_compression_options, true, route_tag);
+    bt.ratoa = AllToAllCommunicatorAccess::make(rpart.tbl->view(), rslice, group, communicator,
+                                                right_compression_options, true, route_tag);
     bt.lrecv = bt.latoa->allocate_communicated_table();
     bt.rrecv = bt.ratoa->allocate_communicated_table();
     bt.ln = bt.lrecv->num_rows();
@@ -2139,6 +2518,26 @@ std::unique_ptr<cudf::table> distributed_inner_join(
 
 /* ------------------------------------------------------------- shuffle_on */
 
+static std::unique_ptr<cudf::table> shuffle_on_tagged(
+  cudf::table_view const& input, std::vector<cudf::size_type> const& on_columns,
+  CommunicationGroup comm_group, Communicator* communicator,
+  std::vector<ColumnCompressionOptions> compression_options, cudf::hash_id hash_function,
+  uint32_t hash_seed, bool report_timing, void* preallocated_pinned_buffer, uint32_t route_tag)
+{
+  DJ_CHECK_ERROR(on_columns.size() >= 1, "shuffle_on: at least one key column");
+  const int hash_fn =
+    hash_function == cudf::hash_id::HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3;
+  DJ_CHECK_ERROR(on_columns.size() <= 4, "shuffle_on: up to 4 key columns supported");
+  validate_compression(input, compression_options);
+  PartitionedTable part = place_rows(input, on_columns, comm_group.size(), hash_fn, hash_seed);
+  auto atoa = AllToAllCommunicatorAccess::make(part.tbl->view(), part.offsets, comm_group,
+                                               communicator, compression_options, false,
+                                               route_tag);
+  auto out = atoa->allocate_communicated_table();
+  atoa->launch_communication(out->mutable_view(), report_timing, preallocated_pinned_buffer);
+  return out;
+}
+
 std::unique_ptr<cudf::table> shuffle_on(cudf::table_view const& input,
                                         std::vector<cudf::size_type> const& on_columns,
                                         CommunicationGroup comm_group,
@@ -2149,17 +2548,9 @@ std::unique_ptr<cudf::table> shuffle_on(cudf::table_view const& input,
                                         bool report_timing,
                                         void* preallocated_pinned_buffer)
 {
-  DJ_CHECK_ERROR(on_columns.size() >= 1, "shuffle_on: at least one key column");
-  const int hash_fn =
-    hash_function == cudf::hash_id::HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3;
-  DJ_CHECK_ERROR(on_columns.size() <= 4, "shuffle_on: up to 4 key columns supported");
-  validate_compression(input, compression_options);
-  PartitionedTable part = place_rows(input, on_columns, comm_group.size(), hash_fn, hash_seed);
-  AllToAllCommunicator atoa(part.tbl->view(), part.offsets, comm_group, communicator,
-                            compression_options, false);
-  auto out = atoa.allocate_communicated_table();
-  atoa.launch_communication(out->mutable_view(), report_timing, preallocated_pinned_buffer);
-  return out;
+  return shuffle_on_tagged(input, on_columns, comm_group, communicator,
+                           std::move(compression_options), hash_function, hash_seed,
+                           report_timing, preallocated_pinned_buffer, 0u);
 }
 
 std::unique_ptr<cudf::table> shuffle_on(cudf::table_view const& input,
@@ -2187,6 +2578,7 @@ std::unique_ptr<cudf::table> distribute_table(cudf::table_view global_table,
   const int G = communicator->mpi_size;
   const int rank = communicator->mpi_rank;
   hipStream_t st = dj_rt_stream();
+  check_no_masks(global_table, "distribute_table");
 
   /* schema + per-rank row counts: root sends [nrows_r, ncols, dtype ids...] */
   std::vector<int64_t> header(2 + kMaxSchemaCols, 0);
@@ -2269,6 +2661,7 @@ std::unique_ptr<cudf::table> collect_tables(cudf::table_view table, Communicator
   const int G = communicator->mpi_size;
   const int rank = communicator->mpi_rank;
   CommunicationGroup group(G, 1, rank);
+  check_no_masks(table, "collect_tables");
 
   /* per-rank row counts to root via communicate_sizes (send all rows to
    * local rank 0) */
@@ -2326,6 +2719,25 @@ cudf::table_view view_from_descs(const dj_col_desc* cols, int nc, int64_t n)
                      cols[c].chars, cols[c].chars_bytes);
     else
       v.emplace_back(data_type((type_id)cols[c].type_id), (cudf::size_type)n, cols[c].data);
+  }
+  return cudf::table_view(v);
+}
+
+/* dj_ncol_desc[nc] -> table view of n rows, masks attached */
+cudf::table_view view_from_ndescs(const dj_ncol_desc* cols, int nc, int64_t n)
+{
+  using cudf::data_type;
+  using cudf::type_id;
+  std::vector<cudf::column_view> v;
+  for (int c = 0; c < nc; c++) {
+    const auto* mask = (const cudf::bitmask_type*)cols[c].null_mask;
+    const cudf::size_type nulls = mask ? (cudf::size_type)cols[c].null_count : 0;
+    if ((type_id)cols[c].type_id == type_id::STRING)
+      v.emplace_back(data_type(type_id::STRING), (cudf::size_type)n, cols[c].data,
+                     cols[c].chars, cols[c].chars_bytes, mask, nulls);
+    else
+      v.emplace_back(data_type((type_id)cols[c].type_id), (cudf::size_type)n, cols[c].data,
+                     mask, nulls);
   }
   return cudf::table_view(v);
 }
@@ -2577,6 +2989,114 @@ void* dj_cpp_partition_cols(const dj_col_desc* cols, int nc, int64_t n, const in
                hash_function == DJ_HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3, seed);
   for (int i = 0; i <= nparts; i++) h_offsets[i] = part.offsets[(size_t)i];
   return part.tbl.release();
+}
+
+/* the nullable-descriptor forms of the three entry points above */
+void* dj_cpp_distributed_inner_join_ncols_multi(void* comm, const dj_ncol_desc* lcols, int nl,
+                                                int64_t ln, const dj_ncol_desc* rcols, int nr,
+                                                int64_t rn, const int32_t* lon,
+                                                const int32_t* ron, int nkeys, int over_decom,
+                                                int report_timing)
+{
+  auto left = view_from_ndescs(lcols, nl, ln);
+  auto right = view_from_ndescs(rcols, nr, rn);
+  std::vector<cudf::size_type> lo(lon, lon + nkeys), ro(ron, ron + nkeys);
+  auto lopts = generate_compression_options_distributed(left, false);
+  auto ropts = generate_compression_options_distributed(right, false);
+  auto result = distributed_inner_join(left, right, lo, ro, (Communicator*)comm, lopts,
+                                       ropts, over_decom, report_timing != 0, nullptr, 1);
+  return result.release();
+}
+
+void* dj_cpp_shuffle_on_ncols(void* comm, const dj_ncol_desc* cols, int nc, int64_t n,
+                              const int32_t* on, int nkeys, int hash_function, uint32_t seed,
+                              int compression)
+{
+  cudf::table_view input = view_from_ndescs(cols, nc, n);
+  std::vector<cudf::size_type> keys(on, on + nkeys);
+  auto opts = generate_compression_options_distributed(input, compression != 0);
+  auto result = shuffle_on(input, keys, (Communicator*)comm, opts, to_hash_id(hash_function),
+                           seed, false, nullptr);
+  return result.release();
+}
+
+void* dj_cpp_partition_ncols(const dj_ncol_desc* cols, int nc, int64_t n, const int32_t* on,
+                             int nkeys, int nparts, int hash_function, uint32_t seed,
+                             int64_t* h_offsets)
+{
+  DJ_CHECK_ERROR(nkeys >= 1 && nkeys <= 4, "partition: 1..4 key columns");
+  DJ_CHECK_ERROR(nparts >= 1 && nparts <= dj::kMaxPartitions, "partition: 1..1024 parts");
+  std::vector<cudf::size_type> keys(on, on + nkeys);
+  PartitionedTable part =
+    place_rows(view_from_ndescs(cols, nc, n), keys, nparts,
+               hash_function == DJ_HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3, seed);
+  for (int i = 0; i <= nparts; i++) h_offsets[i] = part.offsets[(size_t)i];
+  return part.tbl.release();
+}
+
+const void* dj_table_column_null_mask(void* tbl, int i)
+{
+  return ((const cudf::table*)tbl)->get_column(i).null_mask();
+}
+int64_t dj_table_column_null_count(void* tbl, int i)
+{
+  return ((const cudf::table*)tbl)->get_column(i).null_count();
+}
+
+/* test/bench hook for the mask gather (include/distributed_join.h) */
+void dj_gather_bitmasks(const void* const* h_src_masks, void* const* h_dst_masks, int ncols,
+                        const int64_t* d_idx, int64_t n, int64_t* h_null_counts, int reps,
+                        double* h_ms, int cols_per_launch)
+{
+  hipStream_t st = dj_rt_stream();
+  DJ_CHECK_ERROR(ncols >= 0 && ncols <= dj::kMaxSchemaCols, "gather_bitmasks: <= 32 columns");
+  dj::BitmaskGatherDesc bd{};
+  bd.ncols = ncols;
+  for (int c = 0; c < ncols; c++) {
+    bd.src[c] = (const uint32_t*)h_src_masks[c];
+    bd.dst[c] = (uint32_t*)h_dst_masks[c];
+  }
+  DBuf d_counts(dj::kMaxSchemaCols * 4);
+  hipEvent_t e0, e1;
+  DJ_HIP_CALL(hipEventCreate(&e0));
+  DJ_HIP_CALL(hipEventCreate(&e1));
+  for (int r = 0; r < (reps > 0 ? reps : 1); r++) {
+    DJ_HIP_CALL(hipMemsetAsync(d_counts.p, 0, dj::kMaxSchemaCols * 4, st));
+    DJ_HIP_CALL(hipEventRecord(e0, st));
+    dj::gather_bitmasks(bd, d_idx, n, (uint32_t*)d_counts.p, st,
+                        cols_per_launch > 0 ? cols_per_launch : dj::kMaskColsPerLaunch);
+    DJ_HIP_CALL(hipEventRecord(e1, st));
+    DJ_HIP_CALL(hipEventSynchronize(e1));
+    float ms = 0.f;
+    DJ_HIP_CALL(hipEventElapsedTime(&ms, e0, e1));
+    if (h_ms) h_ms[r] = ms;
+  }
+  DJ_HIP_CALL(hipEventDestroy(e0));
+  DJ_HIP_CALL(hipEventDestroy(e1));
+  uint32_t h_counts[dj::kMaxSchemaCols];
+  DJ_HIP_CALL(hipMemcpy(h_counts, d_counts.p, sizeof(h_counts), hipMemcpyDeviceToHost));
+  for (int c = 0; c < ncols; c++) h_null_counts[c] = h_counts[c];
+}
+
+/* test hook for the mask segment copy + null count (include/distributed_join.h) */
+int64_t dj_copy_bitmask_segments(const void* const* h_src_masks, const int64_t* h_src_bits,
+                                 const int64_t* h_nbits, int S, void* d_dst)
+{
+  hipStream_t st = dj_rt_stream();
+  std::vector<BitSeg> segs;
+  int64_t total = 0;
+  for (int i = 0; i < S; i++) {
+    segs.push_back(BitSeg{(const uint32_t*)h_src_masks[i], h_src_bits[i], h_nbits[i]});
+    total += h_nbits[i];
+  }
+  DBuf table = copy_bit_segments(segs, (uint32_t*)d_dst, st);
+  DBuf cnt(8);
+  DJ_HIP_CALL(hipMemsetAsync(cnt.p, 0, 8, st));
+  dj::count_unset_bits((const uint32_t*)d_dst, total, (unsigned long long*)cnt.p, st);
+  unsigned long long h = 0;
+  DJ_HIP_CALL(hipMemcpyAsync(&h, cnt.p, 8, hipMemcpyDeviceToHost, st));
+  DJ_HIP_CALL(hipStreamSynchronize(st));
+  return (int64_t)h;
 }
 
 /* test/bench hook for the table gather (include/distributed_join.h) */

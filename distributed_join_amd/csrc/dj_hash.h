@@ -33,6 +33,18 @@
  * value and drops collisions by comparing the real columns (strings: length,
  * then bytes). HASH_IDENTITY has no STRING form (cuDF has none either).
  *
+ * Null keys: a valid row of a nullable key column places exactly as it would
+ * without the mask (so a mask that marks no row null changes nothing). A null
+ * key element contributes the element hash 0xFFFFFFFF (cuDF's row-hasher
+ * convention for a null element), whatever is stored under it:
+ *   - single integer key, HASH_MURMUR3 and HASH_IDENTITY alike:
+ *       hash = 0xFFFFFFFF, partition = 0xFFFFFFFF % nparts;
+ *   - in the fused chain above: v_c = 0xFFFFFFFF for a null element of
+ *     column c (integer-rep or STRING), the other columns as usual.
+ * The join treats null as equal to null (cudf::inner_join's default
+ * null_equality::EQUAL, which the reference call relies on): the tuple
+ * filter compares validity first and values only where both are valid.
+ *
  * Plain C99; compiles under gcc/g++/hipcc.
  */
 #ifndef DJ_HASH_H

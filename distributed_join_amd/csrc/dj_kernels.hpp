@@ -224,11 +224,19 @@ __host__ __device__ __forceinline__ int64_t load_key_i64(const void* p, int kind
     default: return (int64_t)((const uint8_t*)p)[i];
   }
 }
+/* the element hash a null key element contributes (cuDF's row-hasher
+ * convention; spec in dj_hash.h) */
+constexpr uint32_t kNullKeyHash = 0xFFFFFFFFu;
 struct TupleKeyCol {
   const void* data;
   const uint8_t* chars;
   int kind;
+  const uint32_t* valid; /* validity mask, or nullptr: every element valid */
 };
+__host__ __device__ __forceinline__ bool key_is_valid(const uint32_t* valid, int64_t i)
+{
+  return valid == nullptr || ((valid[i >> 5] >> (i & 31)) & 1u);
+}
 struct TupleKeys {
   TupleKeyCol l[4], r[4];
   int nk;
@@ -298,6 +306,37 @@ enum {
 };
 void gather_table(const GatherCol* cols, int ncols, const int64_t* d_idx, int64_t n, int mode,
                   hipStream_t s);
+
+/* ----- validity masks (dj_bitmask.hip; cuDF layout: row i = bit i % 32 of
+ * uint32 word i / 32, 1 = valid, nullptr = all valid) ----- */
+struct BitmaskGatherDesc {
+  const uint32_t* src[kMaxSchemaCols]; /* nullptr: every gathered bit is 1 */
+  uint32_t* dst[kMaxSchemaCols];       /* 8-byte aligned, roundup(n, 64) / 8 bytes */
+  int ncols;
+};
+/* columns one gather_bitmasks launch takes: the kernel handles up to
+ * kMaxSchemaCols, but a launch that interleaves many source masks loses their
+ * cache residency, so the engine launches once per column */
+constexpr int kMaskColsPerLaunch = 1;
+/* dst_c bit i = src_c bit idx[i], i in [0, n); dst bits [n, roundup(n, 64))
+ * are written 0. d_null_counts[c] (caller-zeroed, kMaxSchemaCols entries) is
+ * advanced by the number of 0 bits written to column c among the n rows. */
+void gather_bitmasks(const BitmaskGatherDesc& desc, const int64_t* d_idx, int64_t n,
+                     uint32_t* d_null_counts, hipStream_t s,
+                     int cols_per_launch = kMaskColsPerLaunch);
+/* Concatenate S bit ranges into d_dst. d_segments is one device block of
+ * 8-byte entries: S source mask pointers (nullptr = all valid), S source bit
+ * offsets, then S+1 destination bit offsets — non-decreasing, [0] = 0,
+ * [S] = total_bits, so segment s fills destination bits
+ * [dst_bit[s], dst_bit[s+1]) (zero length allowed). Writes the
+ * ceil(total_bits / 32) destination words whole, bits past total_bits as 0;
+ * of segment s it reads only source words src_bit/32 ..
+ * (src_bit + nbits - 1)/32. */
+void copy_bitmask_segments(const void* d_segments, int S, int64_t total_bits, uint32_t* d_dst,
+                           hipStream_t s);
+/* *d_count (caller-zeroed) += number of 0 bits among the first n of d_mask */
+void count_unset_bits(const uint32_t* d_mask, int64_t n, unsigned long long* d_count,
+                      hipStream_t s);
 
 /* ----- small utilities ----- */
 void fill_i64(int64_t* d_dst, int64_t value, int64_t n, hipStream_t s);

@@ -557,7 +557,12 @@ __global__ void filter_tuple_matches_mixed_kernel(TupleKeys keys, const int64_t*
     for (int c = 0; c < keys.nk && eq; c++) {
       const TupleKeyCol& lc = keys.l[c];
       const TupleKeyCol& rc = keys.r[c];
-      if (lc.kind == kKeyStr) {
+      /* null_equality::EQUAL: null matches null and no valid element; the
+       * value (and string size) stored under a null is never read */
+      const bool lv = key_is_valid(lc.valid, a), rv = key_is_valid(rc.valid, b);
+      if (!lv || !rv) {
+        eq = lv == rv;
+      } else if (lc.kind == kKeyStr) {
         const int32_t* lo = (const int32_t*)lc.data;
         const int32_t* ro = (const int32_t*)rc.data;
         const int32_t l0 = lo[a], r0 = ro[b];

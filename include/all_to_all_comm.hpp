@@ -151,6 +151,20 @@ class AllToAllCommunicator {
   std::vector<cudf::size_type> send_offsets;
   std::vector<int64_t> recv_offsets;
   std::vector<ColumnCompressionOptions> compression_options;
+  /* bit c: column c carries a validity mask on some rank of the group, so
+   * its mask slices travel and the communicated column gets a mask (agreed
+   * in the constructor's row-count exchange) */
+  uint32_t nullable_cols{0};
+  /* the constructor behind the public ones; route_tag (2 bits) rides the
+   * row-count exchange and must be equal on every rank of the group —
+   * distributed_inner_join tags the route its nullability selected */
+  AllToAllCommunicator(cudf::table_view input_table,
+                       std::vector<cudf::size_type> offsets,
+                       CommunicationGroup comm_group,
+                       Communicator* communicator,
+                       std::vector<ColumnCompressionOptions> compression_options,
+                       bool explicit_copy_to_current_rank,
+                       uint32_t route_tag);
   /* strings machinery (reference all_to_all_comm.hpp:349-360: per string
    * column the char-offset boundaries per peer, plus device buffers of row
    * sizes to send / received — sizes, not offsets, go on the wire). Opaque

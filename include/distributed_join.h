@@ -227,6 +227,64 @@ typedef struct {
 void dj_gather_columns(const dj_gather_desc* descs, int ncols, const int64_t* d_idx, int64_t n,
                        int mode, int reps, double* h_ms);
 
+/* ---------------- nullable columns (validity masks, cuDF layout: row i is
+ * bit i % 32, LSB first, of uint32 word i / 32; 1 = valid; bits past n and
+ * the values under a null row are unspecified). dj_ncol_desc is dj_col_desc
+ * plus the mask: null_mask is a device pointer or NULL ("no nulls"),
+ * null_count the number of null rows (0 when null_mask is NULL). Null keys
+ * join with null_equality::EQUAL (null matches null and no valid key), the
+ * default of the cudf::inner_join call the reference makes
+ * (distributed_join.cpp:79); a null key element places on the element hash
+ * 0xFFFFFFFF (csrc/dj_hash.h). An output column has a mask exactly when its
+ * source column had one. The *_cols entry points above stay mask-free. */
+typedef struct {
+  int type_id;
+  const void* data;
+  const void* chars;
+  int64_t chars_bytes;
+  const void* null_mask;
+  int64_t null_count;
+} dj_ncol_desc;
+
+/* dj_cpp_distributed_inner_join_cols_multi over nullable descriptors */
+void* dj_cpp_distributed_inner_join_ncols_multi(void* comm, const dj_ncol_desc* lcols, int nl,
+                                                int64_t ln, const dj_ncol_desc* rcols, int nr,
+                                                int64_t rn, const int32_t* lon,
+                                                const int32_t* ron, int nkeys, int over_decom,
+                                                int report_timing);
+/* dj_cpp_shuffle_on_cols over nullable descriptors */
+void* dj_cpp_shuffle_on_ncols(void* comm, const dj_ncol_desc* cols, int nc, int64_t n,
+                              const int32_t* on, int nkeys, int hash_function, uint32_t seed,
+                              int compression);
+/* dj_cpp_partition_cols over nullable descriptors */
+void* dj_cpp_partition_ncols(const dj_ncol_desc* cols, int nc, int64_t n, const int32_t* on,
+                             int nkeys, int nparts, int hash_function, uint32_t seed,
+                             int64_t* h_offsets);
+/* mask (device pointer, NULL when the column has none) and exact null count
+ * of column i of an opaque table */
+const void* dj_table_column_null_mask(void* tbl, int i);
+int64_t dj_table_column_null_count(void* tbl, int i);
+
+/* test/bench hook for the mask gather kernel: for each of ncols (<= 32)
+ * columns, bit i of d_dst_masks[c] = bit d_idx[i] of d_src_masks[c] (all 1
+ * when that source is NULL), i in [0, n); destination bits [n, roundup(n, 64))
+ * are written 0. h_src_masks / h_dst_masks are HOST arrays of device
+ * pointers; each destination is 8-byte aligned and holds roundup(n, 64) / 8
+ * bytes. h_null_counts (host int64[ncols]) receives the 0 bits written per
+ * column. Runs `reps` times between hipEvent pairs; h_ms (host double[reps],
+ * may be NULL) receives the milliseconds. cols_per_launch: how many columns
+ * one kernel launch takes (1..32), 0 = what the engine uses. Synchronizes. */
+void dj_gather_bitmasks(const void* const* h_src_masks, void* const* h_dst_masks, int ncols,
+                        const int64_t* d_idx, int64_t n, int64_t* h_null_counts, int reps,
+                        double* h_ms, int cols_per_launch);
+/* test hook for the mask segment copy kernel: S bit ranges (host arrays:
+ * device source mask or NULL = all valid, first source bit, length in bits)
+ * land back to back in d_dst, whose ceil(total / 32) words are written whole
+ * with the bits past the total as 0. Returns the number of 0 bits among the
+ * total (through the null-count kernel). Synchronizes. */
+int64_t dj_copy_bitmask_segments(const void* const* h_src_masks, const int64_t* h_src_bits,
+                                 const int64_t* h_nbits, int S, void* d_dst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,9 +16,15 @@
  * as payload. Integer-rep types (signed, unsigned, BOOL8, chrono) and STRING
  * are also valid join/shuffle keys; FLOAT32/FLOAT64 are payload-only (see
  * INTEGRATION.md "Known restrictions").
+ *
+ * Validity: a column may carry a null mask (cuDF layout, see bitmask_type
+ * below). Masks travel with their rows through partition, shuffle and join;
+ * null keys join with null_equality::EQUAL, the default of the
+ * cudf::inner_join call the reference makes.
  */
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -27,6 +33,20 @@
 namespace cudf {
 
 using size_type = int32_t;
+
+/* validity masks, cuDF layout: row i is bit i % 32 (LSB first) of word
+ * i / 32, 1 = valid; a null mask pointer means "no nulls". Bits past size()
+ * and the values stored under a null row are unspecified. Owned masks are
+ * allocated padded to a multiple of 64 bytes. Views carry no offset. */
+using bitmask_type = uint32_t;
+/* cudf::UNKNOWN_NULL_COUNT: an owning column whose mask was (or may have
+ * been) rewritten through mutable_view() counts its nulls on the next
+ * null_count()/view() */
+constexpr size_type UNKNOWN_NULL_COUNT = -1;
+inline constexpr size_t bitmask_allocation_size_bytes(size_type rows)
+{
+  return (((size_t)(rows > 0 ? rows : 0) + 7) / 8 + 63) / 64 * 64;
+}
 
 enum class type_id : int32_t {
   EMPTY = 0,
@@ -132,8 +152,9 @@ constexpr uint32_t DEFAULT_HASH_SEED = 0;
 class column_view {
  public:
   column_view() = default;
-  column_view(data_type type, size_type size, const void* data)
-    : _type(type), _size(size), _data(data)
+  column_view(data_type type, size_type size, const void* data,
+              const bitmask_type* null_mask = nullptr, size_type null_count = 0)
+    : _type(type), _size(size), _data(data), _null_mask(null_mask), _null_count(null_count)
   {
   }
   /* STRING column: `data` = int32 offsets (size+1 entries), plus a chars
@@ -141,12 +162,24 @@ class column_view {
    * reference's strings path relies on (strings_column.cu:39-145).
    * child(0) = offsets view, child(1) = chars view. */
   column_view(data_type type, size_type size, const void* offsets, const void* chars,
-              int64_t chars_bytes)
-    : _type(type), _size(size), _data(offsets), _chars(chars), _chars_size(chars_bytes)
+              int64_t chars_bytes, const bitmask_type* null_mask = nullptr,
+              size_type null_count = 0)
+    : _type(type),
+      _size(size),
+      _data(offsets),
+      _chars(chars),
+      _chars_size(chars_bytes),
+      _null_mask(null_mask),
+      _null_count(null_count)
   {
   }
   data_type type() const { return _type; }
   size_type size() const { return _size; }
+  /* validity: nullable() = a mask is present (it may still mark no row null) */
+  const bitmask_type* null_mask() const { return _null_mask; }
+  size_type null_count() const { return _null_count; }
+  bool nullable() const { return _null_mask != nullptr; }
+  bool has_nulls() const { return _null_count != 0; } /* unknown counts as "may have" */
   template <typename T>
   const T* head() const
   {
@@ -171,22 +204,36 @@ class column_view {
   const void* _data{nullptr};
   const void* _chars{nullptr};
   int64_t _chars_size{0};
+  const bitmask_type* _null_mask{nullptr};
+  size_type _null_count{0};
 };
 
 class mutable_column_view {
  public:
   mutable_column_view() = default;
-  mutable_column_view(data_type type, size_type size, void* data)
-    : _type(type), _size(size), _data(data)
+  mutable_column_view(data_type type, size_type size, void* data,
+                      bitmask_type* null_mask = nullptr, size_type null_count = 0)
+    : _type(type), _size(size), _data(data), _null_mask(null_mask), _null_count(null_count)
   {
   }
   mutable_column_view(data_type type, size_type size, void* offsets, void* chars,
-                      int64_t chars_bytes)
-    : _type(type), _size(size), _data(offsets), _chars(chars), _chars_size(chars_bytes)
+                      int64_t chars_bytes, bitmask_type* null_mask = nullptr,
+                      size_type null_count = 0)
+    : _type(type),
+      _size(size),
+      _data(offsets),
+      _chars(chars),
+      _chars_size(chars_bytes),
+      _null_mask(null_mask),
+      _null_count(null_count)
   {
   }
   data_type type() const { return _type; }
   size_type size() const { return _size; }
+  bitmask_type* null_mask() const { return _null_mask; }
+  size_type null_count() const { return _null_count; }
+  bool nullable() const { return _null_mask != nullptr; }
+  bool has_nulls() const { return _null_count != 0; } /* unknown counts as "may have" */
   template <typename T>
   T* head() const
   {
@@ -196,7 +243,7 @@ class mutable_column_view {
   int64_t chars_size() const { return _chars_size; }
   operator column_view() const
   {
-    return column_view(_type, _size, _data, _chars, _chars_size);
+    return column_view(_type, _size, _data, _chars, _chars_size, _null_mask, _null_count);
   }
 
  private:
@@ -205,6 +252,8 @@ class mutable_column_view {
   void* _data{nullptr};
   void* _chars{nullptr};
   int64_t _chars_size{0};
+  bitmask_type* _null_mask{nullptr};
+  size_type _null_count{0};
 };
 
 /* owning device column (HIP device memory; allocation in dj_cpp_api.hip) */
@@ -227,10 +276,32 @@ class column {
   void* chars() { return _chars; }
   const void* chars() const { return _chars; }
   int64_t chars_size() const { return _chars_size; }
-  column_view view() const { return column_view(_type, _size, _data, _chars, _chars_size); }
+  /* owned validity mask (released through the arena on move-assign and
+   * destruction). set_null_mask adopts a device buffer of at least
+   * bitmask_allocation_size_bytes(size()) bytes from the same arena,
+   * releasing any mask held before; nullptr drops the mask.
+   * allocate_null_mask gives the column a fresh mask of that size, contents
+   * unspecified, and returns it for the caller to fill. */
+  void set_null_mask(void* adopt_device_ptr, size_type null_count);
+  bitmask_type* allocate_null_mask();
+  void set_null_count(size_type null_count) { _null_count = null_count; }
+  bitmask_type* null_mask() { return _null_mask; }
+  const bitmask_type* null_mask() const { return _null_mask; }
+  /* exact; counts on the device (host-synchronous) when unknown */
+  size_type null_count() const;
+  bool nullable() const { return _null_mask != nullptr; }
+  bool has_nulls() const { return null_count() > 0; }
+  column_view view() const
+  {
+    return column_view(_type, _size, _data, _chars, _chars_size, _null_mask, null_count());
+  }
+  /* as in cuDF, handing out a mutable view of a nullable column forgets its
+   * null count: the holder may rewrite the mask */
   mutable_column_view mutable_view()
   {
-    return mutable_column_view(_type, _size, _data, _chars, _chars_size);
+    if (_null_mask != nullptr) _null_count = UNKNOWN_NULL_COUNT;
+    return mutable_column_view(_type, _size, _data, _chars, _chars_size, _null_mask,
+                               _null_count);
   }
 
  private:
@@ -239,6 +310,8 @@ class column {
   void* _data{nullptr};
   void* _chars{nullptr};
   int64_t _chars_size{0};
+  bitmask_type* _null_mask{nullptr};
+  mutable size_type _null_count{0};
 };
 
 class table_view {
