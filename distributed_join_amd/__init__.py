@@ -125,6 +125,11 @@ def lib():
             "dj_table_column_null_count": ([vp, i32], i64),
             "dj_gather_bitmasks": ([vp, vp, i32, vp, i64, vp, i32, vp, i32], None),
             "dj_copy_bitmask_segments": ([vp, vp, vp, i32, vp], i64),
+            "dj_cpp_distributed_join_ncols_multi": ([vp, i32, vp, i32, i64, vp, i32, i64,
+                                                     vp, vp, i32, i32, i32], vp),
+            "dj_mark_rows": ([vp, i64, vp, i32, i32, vp], None),
+            "dj_select_rows": ([vp, i64, i32, vp, i32, vp], i64),
+            "dj_select_rows_tile_rows": ([], i64),
         }
         for name, (argtypes, restype) in sigs.items():
             f = getattr(_lib, name)
@@ -719,6 +724,57 @@ def copy_bitmask_segments(segments, fill=0xFFFFFFFF):
     if not (words[nwords:] == np.uint32(fill)).all():
         raise AssertionError("copy_bitmask_segments wrote past its last destination word")
     return words[:nwords], unpack_mask(words[:nwords], total), int(nulls)
+
+
+# --------------------------------------- left / left semi / left anti joins
+
+# join_kind of include/distributed_join.hpp, as the C ABI passes it
+JOIN_INNER, JOIN_LEFT, JOIN_LEFT_SEMI, JOIN_LEFT_ANTI = 0, 1, 2, 3
+
+
+def cpp_distributed_join_ncols_multi(comm, kind, lcols, ln, rcols, rn, left_on, right_on,
+                                     over_decom=1):
+    """distributed_join of the given kind (JOIN_*) over nullable column
+    descriptors, as cpp_distributed_inner_join_ncols_multi takes them.
+    JOIN_LEFT returns left then right columns, every right-hand column with a
+    mask; JOIN_LEFT_SEMI / JOIN_LEFT_ANTI return the left columns only.
+    Returns (cols, masks) as table_to_numpy_nullable."""
+    la, ra = _pack_ncols(lcols), _pack_ncols(rcols)
+    lon = np.asarray(left_on, dtype=np.int32)
+    ron = np.asarray(right_on, dtype=np.int32)
+    t = lib().dj_cpp_distributed_join_ncols_multi(
+        comm.ptr, int(kind), ctypes.cast(la, ctypes.c_void_p), len(lcols), ln,
+        ctypes.cast(ra, ctypes.c_void_p), len(rcols), rn,
+        lon.ctypes.data, ron.ctypes.data, len(lon), over_decom, 0)
+    return table_to_numpy_nullable(t)
+
+
+MARK_PLAIN, MARK_MERGE, MARK_CHECK, MARK_ENGINE = 0, 1, 2, -1
+
+
+def mark_rows(d_idx_ptr, n, d_bits_ptr, mode=MARK_ENGINE, reps=1):
+    """The row-marking kernel through its test/bench hook: sets bit idx[i] of
+    the caller-zeroed device bitmap for every i < n. mode: MARK_ENGINE, or an
+    OR of MARK_MERGE / MARK_CHECK (MARK_PLAIN = neither). The bitmap is not
+    re-zeroed between repetitions. Returns the per-repetition milliseconds."""
+    ms = np.zeros(max(reps, 1), dtype=np.float64)
+    lib().dj_mark_rows(d_idx_ptr, n, d_bits_ptr, mode, reps, ms.ctypes.data)
+    return ms
+
+
+def select_rows(d_bits_ptr, nrows, want_set, d_out_ptr, reps=1):
+    """The row-selection kernels through their test/bench hook: writes the
+    ascending indices i < nrows whose bit equals want_set to the device array
+    d_out_ptr (room for nrows int64). Returns (count, per-repetition ms)."""
+    ms = np.zeros(max(reps, 1), dtype=np.float64)
+    count = lib().dj_select_rows(d_bits_ptr, nrows, int(bool(want_set)), d_out_ptr, reps,
+                                 ms.ctypes.data)
+    return int(count), ms
+
+
+def select_rows_tile_rows():
+    """Rows one block of select_rows ranks at a time."""
+    return int(lib().dj_select_rows_tile_rows())
 
 
 GATHER_FUSED, GATHER_PER_COLUMN, GATHER_AUTO = 0, 1, 2

@@ -56,6 +56,13 @@ __global__ void iota_i64_kernel(int64_t* dst, int64_t n)
   for (; i < n; i += stride) dst[i] = i;
 }
 
+__global__ void fill_i32_kernel(int32_t* dst, int64_t n, int32_t value)
+{
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) dst[i] = value;
+}
+
 /* narrow integer-rep key column -> the engine's int64 key (sign- or
  * zero-extended per dj::load_key_i64) */
 __global__ void widen_key_kernel(const void* __restrict__ src, int kind, int64_t n,
@@ -1548,9 +1555,11 @@ namespace {
 
 /* gather a STRING column by a row-index permutation: sizes gather -> scan ->
  * chars gather (the reference's thrust::gather + scan strings recipe,
- * strings_column.cu:39-131, as one reusable step) */
+ * strings_column.cu:39-131, as one reusable step). null_tail > 0 appends
+ * that many empty rows behind the n gathered ones (the null right-hand cells
+ * of a left join): their offsets all equal the chars total. */
 std::unique_ptr<cudf::column> gather_string_column(cudf::column_view src, const int64_t* d_idx,
-                                                   int64_t n)
+                                                   int64_t n, int64_t null_tail = 0)
 {
   hipStream_t st = dj_rt_stream();
   DBuf sizes((size_t)(n > 0 ? n : 1) * 4);
@@ -1575,9 +1584,12 @@ std::unique_ptr<cudf::column> gather_string_column(cudf::column_view src, const 
   DJ_CHECK_ERROR(tot64 <= INT32_MAX,
                  "string gather: output chars exceed 2^31 (int32 offsets limit; shrink "
                  "the per-batch output with over_decom or more ranks)");
-  auto col = std::make_unique<cudf::column>((cudf::size_type)n, (int64_t)total);
+  auto col = std::make_unique<cudf::column>((cudf::size_type)(n + null_tail), (int64_t)total);
   DJ_HIP_CALL(hipMemcpyAsync(col->head(), off.p, ((size_t)n + 1) * 4,
                              hipMemcpyDeviceToDevice, st));
+  if (null_tail > 0)
+    hipLaunchKernelGGL(fill_i32_kernel, dim3(grid_for_n(null_tail)), dim3(kBlock), 0, st,
+                       (int32_t*)col->head() + n + 1, null_tail, total);
   dj::gather_chars_from_starts((const uint8_t*)src.chars(), (const int32_t*)starts.p, n,
                                (const int32_t*)col->head(), (uint8_t*)col->chars(), st);
   DJ_HIP_CALL(hipStreamSynchronize(st));
@@ -1590,11 +1602,20 @@ std::unique_ptr<cudf::column> gather_string_column(cudf::column_view src, const 
  * gather"); STRING columns keep gather_string_column. The key column
  * (key_col >= 0) is not gathered: its joined values already sit in key_vals
  * as int64 (each random-line gather of 240 M rows costs ~5 ms; adopting the
- * key buffer is free, narrowing to the key's own width is a streaming copy). */
+ * key buffer is free, narrowing to the key's own width is a streaming copy).
+ *
+ * null_tail >= 0 builds the right-hand side of a left join: every column has
+ * n + null_tail rows, the tail rows are null cells (zero bytes, empty
+ * strings), and EVERY column carries a mask, whether its source had one or
+ * not and also when null_tail is 0. The default, -1, is the plain gather. */
 void gather_table_columns(cudf::table_view src, DBuf& idx, int64_t n, cudf::size_type key_col,
                           DBuf* key_vals, std::vector<std::unique_ptr<cudf::column>>& cols,
-                          hipStream_t st)
+                          hipStream_t st, int64_t null_tail = -1)
 {
+  const int64_t* d_idx = idx.i64();
+  const bool pad = null_tail >= 0;
+  const int64_t tail = pad ? null_tail : 0;
+  DJ_CHECK_ERROR(!pad || key_vals == nullptr, "gather: a null-padded side adopts no key buffer");
   std::vector<dj::GatherCol> gc;
   const int64_t* key_src = nullptr;
   void* key_dst = nullptr;
@@ -1603,7 +1624,7 @@ void gather_table_columns(cudf::table_view src, DBuf& idx, int64_t n, cudf::size
   for (cudf::size_type c = 0; c < src.num_columns(); c++) {
     cudf::column_view v = src.column(c);
     if (v.type().id() == cudf::type_id::STRING) {
-      cols.push_back(gather_string_column(v, idx.i64(), n));
+      cols.push_back(gather_string_column(v, d_idx, n, tail));
       continue;
     }
     const int width = cudf::size_of(v.type());
@@ -1621,25 +1642,31 @@ void gather_table_columns(cudf::table_view src, DBuf& idx, int64_t n, cudf::size
       cols.push_back(std::move(col));
       continue;
     }
-    auto col = std::make_unique<cudf::column>(v.type(), (cudf::size_type)n);
+    auto col = std::make_unique<cudf::column>(v.type(), (cudf::size_type)(n + tail));
     gc.push_back(dj::GatherCol{v.head<void>(), col->head(), width});
+    if (tail > 0)
+      DJ_HIP_CALL(hipMemsetAsync((uint8_t*)col->head() + (size_t)n * width, 0,
+                                 (size_t)tail * width, st));
     cols.push_back(std::move(col));
   }
   dj_timing::Scope t(DJ_PHASE_GATHER, st);
   if (key_dst != nullptr && n > 0)
     hipLaunchKernelGGL(narrow_key_kernel, dim3(grid_for_n(n)), dim3(kBlock), 0, st, key_src, n,
                        key_width, key_dst);
-  dj::gather_table(gc.data(), (int)gc.size(), idx.i64(), n, dj::kGatherAuto, st);
+  dj::gather_table(gc.data(), (int)gc.size(), d_idx, n, dj::kGatherAuto, st);
 
   /* validity: every nullable source column gets an output mask through
    * dj::gather_bitmasks over the same index array (launches of their own,
    * one per column, after the value gather — DESIGN.md §3d), key and STRING
-   * columns included; a mask-free table stops here */
-  if (!any_nullable(src)) return;
+   * columns included; a mask-free table stops here. A null-padded side
+   * masks every column: a null source mask gathers as all valid, and the
+   * tail bits stay 0 from the memset below (gather_bitmasks writes bits
+   * [0, roundup(n, 64)) only, the ones at and past n as 0). */
+  if (!pad && !any_nullable(src)) return;
   std::vector<cudf::column*> masked;
   std::vector<const uint32_t*> msrc;
   for (cudf::size_type c = 0; c < src.num_columns(); c++) {
-    if (!src.column(c).nullable()) continue;
+    if (!pad && !src.column(c).nullable()) continue;
     masked.push_back(cols[first + (size_t)c].get());
     msrc.push_back(src.column(c).null_mask());
   }
@@ -1654,13 +1681,19 @@ void gather_table_columns(cudf::table_view src, DBuf& idx, int64_t n, cudf::size
     for (int k = 0; k < bd.ncols; k++) {
       bd.src[k] = msrc[k0 + (size_t)k];
       bd.dst[k] = masked[k0 + (size_t)k]->allocate_null_mask();
+      if (pad)
+        DJ_HIP_CALL(hipMemsetAsync(
+          bd.dst[k], 0,
+          std::max<size_t>(cudf::bitmask_allocation_size_bytes((cudf::size_type)(n + tail)), 64),
+          st));
     }
-    dj::gather_bitmasks(bd, idx.i64(), n, (uint32_t*)d_counts.p + k0, st);
+    dj::gather_bitmasks(bd, d_idx, n, (uint32_t*)d_counts.p + k0, st);
   }
   std::vector<uint32_t> h_counts(nm);
   DJ_HIP_CALL(hipMemcpyAsync(h_counts.data(), d_counts.p, nm * 4, hipMemcpyDeviceToHost, st));
   DJ_HIP_CALL(hipStreamSynchronize(st));
-  for (size_t k = 0; k < nm; k++) masked[k]->set_null_count((cudf::size_type)h_counts[k]);
+  for (size_t k = 0; k < nm; k++)
+    masked[k]->set_null_count((cudf::size_type)(h_counts[k] + (uint32_t)tail));
 }
 
 /* stable hash-partition of an arbitrary table into nparts contiguous ranges:
@@ -1819,21 +1852,29 @@ std::pair<JoinOut, int64_t> run_bucket_join(const int64_t* lk, const int64_t* lp
   }
 }
 
+/* appends one 0-row column per column of t; masked where the source is, or
+ * everywhere (the right-hand side of a left join) */
+void append_empty_columns(cudf::table_view t, bool all_masked,
+                          std::vector<std::unique_ptr<cudf::column>>& cols)
+{
+  for (cudf::size_type c = 0; c < t.num_columns(); c++) {
+    if (is_string(t.column(c)))
+      cols.push_back(std::make_unique<cudf::column>((cudf::size_type)0, (int64_t)0));
+    else
+      cols.push_back(std::make_unique<cudf::column>(t.column(c).type(), (cudf::size_type)0));
+    if (all_masked || t.column(c).nullable()) {
+      cols.back()->allocate_null_mask();
+      cols.back()->set_null_count(0);
+    }
+  }
+}
+
 /* the empty table with a join's output schema: left's columns, then right's */
 std::unique_ptr<cudf::table> empty_join_result(cudf::table_view left, cudf::table_view right)
 {
   std::vector<std::unique_ptr<cudf::column>> cols;
-  for (cudf::table_view const& t : {left, right})
-    for (cudf::size_type c = 0; c < t.num_columns(); c++) {
-      if (is_string(t.column(c)))
-        cols.push_back(std::make_unique<cudf::column>((cudf::size_type)0, (int64_t)0));
-      else
-        cols.push_back(std::make_unique<cudf::column>(t.column(c).type(), (cudf::size_type)0));
-      if (t.column(c).nullable()) {
-        cols.back()->allocate_null_mask();
-        cols.back()->set_null_count(0);
-      }
-    }
+  append_empty_columns(left, false, cols);
+  append_empty_columns(right, false, cols);
   return std::make_unique<cudf::table>(std::move(cols));
 }
 
@@ -1868,6 +1909,70 @@ std::unique_ptr<cudf::table> assemble_join_output(cudf::table_view left, cudf::t
   return std::make_unique<cudf::table>(std::move(cols));
 }
 
+/* LEFT / LEFT_SEMI / LEFT_ANTI from the pair list: out.o1[0..nout) are the
+ * left row indices of the matching pairs (after the collision filter),
+ * out.o3 the right ones; li_cap is the number of elements out.o1 has room
+ * for. The matched left rows are marked in a bitmap of ln bits
+ * (dj::mark_rows) and the kept row set is read back in ascending order
+ * (dj::select_rows), so that the gather it feeds streams through the source.
+ *   semi / anti: the left columns of the marked / unmarked rows
+ *   left:        left columns by [o1 , unmatched] in one gather; right
+ *                columns gathered for the nout pairs and null-padded for the
+ *                nun unmatched rows in the same allocation — the inner part
+ *                is written once
+ * Host-synchronous. */
+std::unique_ptr<cudf::table> assemble_left_kind(join_kind kind, cudf::table_view left,
+                                                cudf::table_view right, JoinOut& out,
+                                                int64_t nout, int64_t li_cap)
+{
+  hipStream_t st = dj_rt_stream();
+  const int64_t ln = left.num_rows();
+  std::vector<std::unique_ptr<cudf::column>> cols;
+  if (ln == 0) {
+    append_empty_columns(left, false, cols);
+    if (kind == join_kind::LEFT) append_empty_columns(right, true, cols);
+    return std::make_unique<cudf::table>(std::move(cols));
+  }
+  const size_t bitmap_bytes = (size_t)((ln + 31) / 32) * 4;
+  DBuf bits(bitmap_bytes), count(8);
+  DBuf scratch(dj::select_rows_scratch_bytes(ln));
+  DJ_HIP_CALL(hipMemsetAsync(bits.p, 0, bitmap_bytes, st));
+  dj::mark_rows(out.o1.i64(), nout, (uint32_t*)bits.p, st);
+  int64_t nsel = 0;
+
+  if (kind != join_kind::LEFT) {
+    DBuf sel((size_t)ln * 8);
+    dj::select_rows((const uint32_t*)bits.p, ln, kind == join_kind::LEFT_SEMI, sel.i64(),
+                    count.i64(), st, scratch.p);
+    DJ_HIP_CALL(hipMemcpyAsync(&nsel, count.p, 8, hipMemcpyDeviceToHost, st));
+    DJ_HIP_CALL(hipStreamSynchronize(st));
+    if (nsel == 0)
+      append_empty_columns(left, false, cols);
+    else
+      gather_table_columns(left, sel, nsel, -1, nullptr, cols, st);
+    DJ_HIP_CALL(hipStreamSynchronize(st));
+    return std::make_unique<cudf::table>(std::move(cols));
+  }
+
+  /* the unmatched rows go straight behind the pairs' left indices */
+  if (li_cap < nout + ln) {
+    DBuf wide((size_t)(nout + ln) * 8);
+    if (nout > 0)
+      DJ_HIP_CALL(hipMemcpyAsync(wide.p, out.o1.p, (size_t)nout * 8, hipMemcpyDeviceToDevice, st));
+    DJ_HIP_CALL(hipStreamSynchronize(st));  // the old array returns to the pool
+    out.o1 = std::move(wide);
+  }
+  dj::select_rows((const uint32_t*)bits.p, ln, false, out.o1.i64() + nout, count.i64(), st,
+                  scratch.p);
+  DJ_HIP_CALL(hipMemcpyAsync(&nsel, count.p, 8, hipMemcpyDeviceToHost, st));
+  DJ_HIP_CALL(hipStreamSynchronize(st));
+  DJ_CHECK_ERROR(nout + nsel <= INT32_MAX, "left join: output exceeds 2^31 rows");
+  gather_table_columns(left, out.o1, nout + nsel, -1, nullptr, cols, st);
+  gather_table_columns(right, out.o3, nout, -1, nullptr, cols, st, nsel);
+  DJ_HIP_CALL(hipStreamSynchronize(st));
+  return std::make_unique<cudf::table>(std::move(cols));
+}
+
 dj::TupleKeyCol tuple_key_col(cudf::column_view col)
 {
   dj::TupleKeyCol d{};
@@ -1878,8 +1983,9 @@ dj::TupleKeyCol tuple_key_col(cudf::column_view col)
   return d;
 }
 
-/* local inner join of two tables via the bucketed-LDS engine; returns
- * left-cols + right-cols with keys duplicated, row order unspecified.
+/* local join of two tables via the bucketed-LDS engine. INNER returns
+ * left-cols + right-cols with keys duplicated, row order unspecified; the
+ * other kinds build the same pair list and hand it to assemble_left_kind.
  * A single integer key column is the engine's key as it is (widened when
  * narrow). Composite keys, and STRING keys even alone, bucket-join on the
  * fused key chain (fuse_keys: the row hash stands in for a string) with
@@ -1887,10 +1993,12 @@ dj::TupleKeyCol tuple_key_col(cudf::column_view col)
  * columns — the single-key engine does the heavy lifting; only
  * placement/equality semantics widen. (Reference: cudf::inner_join on
  * arbitrary left_on/right_on, distributed_join.cpp:71-132.) */
-std::unique_ptr<cudf::table> local_inner_join(cudf::table_view left, cudf::table_view right,
-                                              std::vector<cudf::size_type> const& lon,
-                                              std::vector<cudf::size_type> const& ron)
+std::unique_ptr<cudf::table> local_join(join_kind kind, cudf::table_view left,
+                                        cudf::table_view right,
+                                        std::vector<cudf::size_type> const& lon,
+                                        std::vector<cudf::size_type> const& ron)
 {
+  const bool inner = kind == join_kind::INNER;
   DJ_CHECK_ERROR(lon.size() == ron.size(), "left_on/right_on must have equal length");
   bool str_keys = false;
   for (size_t c = 0; c < lon.size(); c++) {
@@ -1905,7 +2013,12 @@ std::unique_ptr<cudf::table> local_inner_join(cudf::table_view left, cudf::table
                      any_nullable_key(right, ron);
   hipStream_t st = dj_rt_stream();
   const int64_t ln = left.num_rows(), rn = right.num_rows();
-  if (ln == 0 || rn == 0) return empty_join_result(left, right);  // distributed_join.cpp:76-83
+  if (ln == 0 || rn == 0) {
+    if (inner) return empty_join_result(left, right);  // distributed_join.cpp:76-83
+    /* no pair list to build: every left row (if any) is unmatched */
+    JoinOut none;
+    return assemble_left_kind(kind, left, right, none, 0, 0);
+  }
 
   /* the output's key columns: known only for a single integer key (a fused
    * key's columns are gathered like any other) */
@@ -1925,13 +2038,16 @@ std::unique_ptr<cudf::table> local_inner_join(cudf::table_view left, cudf::table
   /* general path payload = row index; the partition kernels synthesize it
    * (pay == nullptr -> i), so no iota arrays to materialize or re-read
    * (2.4 GB/step at the TPC-H shape) */
-  const bool pairs = joins_i64_pairs(left, right, left_key, right_key);
+  /* the other kinds need the left row of every pair, so they always join on
+   * row-index payloads, 2 x INT64 tables included */
+  const bool pairs = inner && joins_i64_pairs(left, right, left_key, right_key);
   const int64_t* lp = pairs ? left.column(1).head<int64_t>() : nullptr;
   const int64_t* rp = pairs ? right.column(1).head<int64_t>() : nullptr;
 
   auto joined = run_bucket_join(lk, lp, ln, rk, rp, rn);
   JoinOut& out = joined.first;
   int64_t nout = joined.second;
+  int64_t li_cap = out.cap;  // elements the left-index array has room for
   if (fused) {
     /* collision filter: keep the (li, ri) pairs whose REAL key tuples are
      * equal (the bucket join matched on the fused hash; unequal tuples
@@ -1943,18 +2059,28 @@ std::unique_ptr<cudf::table> local_inner_join(cudf::table_view left, cudf::table
       tk.l[c] = tuple_key_col(left.column(lon[c]));
       tk.r[c] = tuple_key_col(right.column(ron[c]));
     }
-    DBuf li2((size_t)std::max<int64_t>(nout, 1) * 8);
+    /* a left join appends its unmatched rows (at most ln) behind the pairs */
+    li_cap = std::max<int64_t>(nout, 1) + (kind == join_kind::LEFT ? ln : 0);
+    DBuf li2((size_t)li_cap * 8);
     DBuf ri2((size_t)std::max<int64_t>(nout, 1) * 8);
     out.clear(st);
     dj::filter_tuple_matches_mixed(tk, out.o1.i64(), out.o3.i64(), nout, li2.i64(), ri2.i64(),
                                    (unsigned long long*)out.counter(), st);
     DJ_HIP_CALL(hipMemcpyAsync(&nout, out.counter(), 8, hipMemcpyDeviceToHost, st));
     DJ_HIP_CALL(hipStreamSynchronize(st));
-    if (nout == 0) return empty_join_result(left, right);
+    if (nout == 0 && inner) return empty_join_result(left, right);
     out.o1 = std::move(li2);
     out.o3 = std::move(ri2);
   }
+  if (!inner) return assemble_left_kind(kind, left, right, out, nout, li_cap);
   return assemble_join_output(left, right, out, nout, left_key, right_key);
+}
+
+std::unique_ptr<cudf::table> local_inner_join(cudf::table_view left, cudf::table_view right,
+                                              std::vector<cudf::size_type> const& lon,
+                                              std::vector<cudf::size_type> const& ron)
+{
+  return local_join(join_kind::INNER, left, right, lon, ron);
 }
 
 /* rebase a part's offsets by a constant and append (STRING concat) */
@@ -2513,6 +2639,125 @@ std::unique_ptr<cudf::table> distributed_inner_join(
               << std::endl;
 
   return finalize_batches(batches, left_key, right_key, report_timing, communicator->mpi_rank);
+}
+
+/* ------------------------------------------- left / left semi / left anti */
+
+std::unique_ptr<cudf::table> distributed_join(
+  join_kind kind,
+  cudf::table_view left,
+  cudf::table_view right,
+  std::vector<cudf::size_type> const& left_on,
+  std::vector<cudf::size_type> const& right_on,
+  Communicator* communicator,
+  std::vector<ColumnCompressionOptions> left_compression_options,
+  std::vector<ColumnCompressionOptions> right_compression_options,
+  int over_decom_factor,
+  bool report_timing,
+  void* preallocated_pinned_buffer,
+  int nvlink_domain_size)
+{
+  if (kind == join_kind::INNER)
+    return distributed_inner_join(left, right, left_on, right_on, communicator,
+                                  std::move(left_compression_options),
+                                  std::move(right_compression_options), over_decom_factor,
+                                  report_timing, preallocated_pinned_buffer, nvlink_domain_size);
+  DJ_CHECK_ERROR(kind == join_kind::LEFT || kind == join_kind::LEFT_SEMI ||
+                   kind == join_kind::LEFT_ANTI,
+                 "distributed_join: unknown join kind");
+  DJ_CHECK_ERROR(left_on.size() == right_on.size() && !left_on.empty(),
+                 "left_on/right_on must name the same number of key columns");
+  DJ_CHECK_ERROR(left_on.size() <= 4, "up to 4 join key columns supported");
+  validate_compression(left, left_compression_options);
+  validate_compression(right, right_compression_options);
+  check_key_pairs(left, right, left_on, right_on);
+
+  /* a semi / anti join asks of the right table only whether a key exists:
+   * its other columns stay home, before any stage that communicates */
+  std::vector<cudf::size_type> ron = right_on;
+  if (kind != join_kind::LEFT) {
+    std::vector<cudf::column_view> key_cols;
+    std::vector<ColumnCompressionOptions> key_opts;
+    for (size_t k = 0; k < right_on.size(); k++) {
+      key_cols.push_back(right.column(right_on[k]));
+      if ((size_t)right_on[k] < right_compression_options.size())
+        key_opts.push_back(right_compression_options[(size_t)right_on[k]]);
+      ron[k] = (cudf::size_type)k;
+    }
+    if (key_opts.size() != key_cols.size()) key_opts.clear();
+    right = cudf::table_view(std::move(key_cols));
+    right_compression_options = std::move(key_opts);
+  }
+
+  const int world = communicator->mpi_size;
+  const int nvl = get_nvl_partition_size(world, nvlink_domain_size < 1 ? 1 : nvlink_domain_size);
+  /* the same inter-domain stage as the inner join's (seed 87654321) */
+  std::unique_ptr<cudf::table> l_ib, r_ib;
+  if (nvl != world) {
+    CommunicationGroup inter(world, nvl, communicator->mpi_rank);
+    l_ib = shuffle_on(left, left_on, inter, communicator, left_compression_options,
+                      cudf::hash_id::HASH_MURMUR3, DJ_SEED_INTER, report_timing,
+                      preallocated_pinned_buffer);
+    r_ib = shuffle_on(right, ron, inter, communicator, right_compression_options,
+                      cudf::hash_id::HASH_MURMUR3, DJ_SEED_INTER, report_timing,
+                      preallocated_pinned_buffer);
+    left = l_ib->view();
+    right = r_ib->view();
+  }
+  if (nvl == 1) return local_join(kind, left, right, left_on, ron);
+
+  /* shuffle + local join, the route composite and nullable keys take in the
+   * inner join: after the shuffle every right row that could match a left
+   * row sits on that row's rank, so matched / unmatched is decided locally.
+   * Every rank takes this route whatever its masks, so there is no route to
+   * disagree on (tag 0); over_decom_factor has no effect here. */
+  CommunicationGroup g2(nvl, 1, communicator->mpi_rank);
+  auto ls = shuffle_on_tagged(left, left_on, g2, communicator, left_compression_options,
+                              cudf::hash_id::HASH_MURMUR3, DJ_SEED_INTRA, report_timing,
+                              preallocated_pinned_buffer, 0u);
+  auto rs = shuffle_on_tagged(right, ron, g2, communicator, right_compression_options,
+                              cudf::hash_id::HASH_MURMUR3, DJ_SEED_INTRA, report_timing,
+                              preallocated_pinned_buffer, 0u);
+  return local_join(kind, ls->view(), rs->view(), left_on, ron);
+}
+
+std::unique_ptr<cudf::table> distributed_left_join(
+  cudf::table_view left, cudf::table_view right, std::vector<cudf::size_type> const& left_on,
+  std::vector<cudf::size_type> const& right_on, Communicator* communicator,
+  std::vector<ColumnCompressionOptions> left_compression_options,
+  std::vector<ColumnCompressionOptions> right_compression_options, int over_decom_factor,
+  bool report_timing, void* preallocated_pinned_buffer, int nvlink_domain_size)
+{
+  return distributed_join(join_kind::LEFT, left, right, left_on, right_on, communicator,
+                          std::move(left_compression_options),
+                          std::move(right_compression_options), over_decom_factor,
+                          report_timing, preallocated_pinned_buffer, nvlink_domain_size);
+}
+
+std::unique_ptr<cudf::table> distributed_left_semi_join(
+  cudf::table_view left, cudf::table_view right, std::vector<cudf::size_type> const& left_on,
+  std::vector<cudf::size_type> const& right_on, Communicator* communicator,
+  std::vector<ColumnCompressionOptions> left_compression_options,
+  std::vector<ColumnCompressionOptions> right_compression_options, int over_decom_factor,
+  bool report_timing, void* preallocated_pinned_buffer, int nvlink_domain_size)
+{
+  return distributed_join(join_kind::LEFT_SEMI, left, right, left_on, right_on, communicator,
+                          std::move(left_compression_options),
+                          std::move(right_compression_options), over_decom_factor,
+                          report_timing, preallocated_pinned_buffer, nvlink_domain_size);
+}
+
+std::unique_ptr<cudf::table> distributed_left_anti_join(
+  cudf::table_view left, cudf::table_view right, std::vector<cudf::size_type> const& left_on,
+  std::vector<cudf::size_type> const& right_on, Communicator* communicator,
+  std::vector<ColumnCompressionOptions> left_compression_options,
+  std::vector<ColumnCompressionOptions> right_compression_options, int over_decom_factor,
+  bool report_timing, void* preallocated_pinned_buffer, int nvlink_domain_size)
+{
+  return distributed_join(join_kind::LEFT_ANTI, left, right, left_on, right_on, communicator,
+                          std::move(left_compression_options),
+                          std::move(right_compression_options), over_decom_factor,
+                          report_timing, preallocated_pinned_buffer, nvlink_domain_size);
 }
 
 
@@ -3098,6 +3343,70 @@ int64_t dj_copy_bitmask_segments(const void* const* h_src_masks, const int64_t* 
   DJ_HIP_CALL(hipStreamSynchronize(st));
   return (int64_t)h;
 }
+
+void* dj_cpp_distributed_join_ncols_multi(void* comm, int kind, const dj_ncol_desc* lcols,
+                                          int nl, int64_t ln, const dj_ncol_desc* rcols, int nr,
+                                          int64_t rn, const int32_t* lon, const int32_t* ron,
+                                          int nkeys, int over_decom, int report_timing)
+{
+  DJ_CHECK_ERROR(kind >= DJ_JOIN_INNER && kind <= DJ_JOIN_LEFT_ANTI, "join kind must be 0..3");
+  auto left = view_from_ndescs(lcols, nl, ln);
+  auto right = view_from_ndescs(rcols, nr, rn);
+  std::vector<cudf::size_type> lo(lon, lon + nkeys), ro(ron, ron + nkeys);
+  auto lopts = generate_compression_options_distributed(left, false);
+  auto ropts = generate_compression_options_distributed(right, false);
+  auto result = distributed_join((join_kind)kind, left, right, lo, ro, (Communicator*)comm,
+                                 lopts, ropts, over_decom, report_timing != 0, nullptr, 1);
+  return result.release();
+}
+
+/* test/bench hooks for the row-set kernels (include/distributed_join.h) */
+void dj_mark_rows(const int64_t* d_idx, int64_t n, void* d_bits, int mode, int reps,
+                  double* h_ms)
+{
+  hipStream_t st = dj_rt_stream();
+  hipEvent_t e0, e1;
+  DJ_HIP_CALL(hipEventCreate(&e0));
+  DJ_HIP_CALL(hipEventCreate(&e1));
+  for (int r = 0; r < (reps > 0 ? reps : 1); r++) {
+    DJ_HIP_CALL(hipEventRecord(e0, st));
+    dj::mark_rows(d_idx, n, (uint32_t*)d_bits, st, mode < 0 ? dj::kMarkDefault : mode);
+    DJ_HIP_CALL(hipEventRecord(e1, st));
+    DJ_HIP_CALL(hipEventSynchronize(e1));
+    float ms = 0.f;
+    DJ_HIP_CALL(hipEventElapsedTime(&ms, e0, e1));
+    if (h_ms) h_ms[r] = ms;
+  }
+  DJ_HIP_CALL(hipEventDestroy(e0));
+  DJ_HIP_CALL(hipEventDestroy(e1));
+}
+
+int64_t dj_select_rows(const void* d_bits, int64_t nrows, int want_set, int64_t* d_out_idx,
+                       int reps, double* h_ms)
+{
+  hipStream_t st = dj_rt_stream();
+  DBuf scratch(dj::select_rows_scratch_bytes(nrows)), count(8);
+  hipEvent_t e0, e1;
+  DJ_HIP_CALL(hipEventCreate(&e0));
+  DJ_HIP_CALL(hipEventCreate(&e1));
+  for (int r = 0; r < (reps > 0 ? reps : 1); r++) {
+    DJ_HIP_CALL(hipEventRecord(e0, st));
+    dj::select_rows((const uint32_t*)d_bits, nrows, want_set != 0, d_out_idx, count.i64(), st,
+                    scratch.p);
+    DJ_HIP_CALL(hipEventRecord(e1, st));
+    DJ_HIP_CALL(hipEventSynchronize(e1));
+    float ms = 0.f;
+    DJ_HIP_CALL(hipEventElapsedTime(&ms, e0, e1));
+    if (h_ms) h_ms[r] = ms;
+  }
+  DJ_HIP_CALL(hipEventDestroy(e0));
+  DJ_HIP_CALL(hipEventDestroy(e1));
+  int64_t h = 0;
+  DJ_HIP_CALL(hipMemcpy(&h, count.p, 8, hipMemcpyDeviceToHost));
+  return h;
+}
+
+int64_t dj_select_rows_tile_rows(void) { return dj::select_rows_tile_rows(); }
 
 /* test/bench hook for the table gather (include/distributed_join.h) */
 void dj_gather_columns(const dj_gather_desc* descs, int ncols, const int64_t* d_idx, int64_t n,

@@ -338,6 +338,32 @@ void copy_bitmask_segments(const void* d_segments, int S, int64_t total_bits, ui
 void count_unset_bits(const uint32_t* d_mask, int64_t n, unsigned long long* d_count,
                       hipStream_t s);
 
+/* ----- row sets (dj_rowset.hip; same bit layout, here 1 = "row is in the
+ * set"): from a join's pair list to the rows a left / semi / anti join keeps */
+/* mark_rows variants, for the benchmark's ablation; the engine runs
+ * kMarkDefault: the wave merge alone. The load check never paid for itself
+ * on MI355X — the atomic OR on the L2-resident bitmap costs what the load
+ * costs. */
+constexpr int kMarkMerge = 1; /* lanes naming one word combine their bits first */
+constexpr int kMarkCheck = 2; /* load the word, skip the atomic when nothing is new */
+constexpr int kMarkDefault = kMarkMerge;
+/* Sets bit d_idx[i] of d_bits for every i < n. The caller zeroes d_bits
+ * (ceil(nrows / 32) words) and guarantees 0 <= d_idx[i] < nrows. Any index may
+ * occur any number of times. Reads d_idx[0..n); writes (atomic OR) only words
+ * that hold a marked bit. */
+void mark_rows(const int64_t* d_idx, int64_t n, uint32_t* d_bits, hipStream_t s,
+               int mode = kMarkDefault);
+/* Writes to d_out_idx, ascending, the i < nrows whose bit of d_bits equals
+ * want_set, and their number to *d_count. Bits at and past nrows in the last
+ * word are ignored. d_out_idx holds as many elements as are selected (nrows
+ * always suffices); d_scratch holds select_rows_scratch_bytes(nrows). Reads
+ * ceil(nrows / 32) words of d_bits. */
+size_t select_rows_scratch_bytes(int64_t nrows);
+void select_rows(const uint32_t* d_bits, int64_t nrows, bool want_set, int64_t* d_out_idx,
+                 int64_t* d_count, hipStream_t s, void* d_scratch);
+/* rows one block of select_rows ranks at a time (tests probe around it) */
+int64_t select_rows_tile_rows();
+
 /* ----- small utilities ----- */
 void fill_i64(int64_t* d_dst, int64_t value, int64_t n, hipStream_t s);
 /* out-of-band join of rows whose key equals the reserved empty sentinel

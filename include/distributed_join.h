@@ -285,6 +285,44 @@ void dj_gather_bitmasks(const void* const* h_src_masks, void* const* h_dst_masks
 int64_t dj_copy_bitmask_segments(const void* const* h_src_masks, const int64_t* h_src_bits,
                                  const int64_t* h_nbits, int S, void* d_dst);
 
+/* ---------------- left / left semi / left anti joins.
+ * dj_cpp_distributed_inner_join_ncols_multi with a join kind after comm:
+ * 0 = INNER (forwards to the inner join), 1 = LEFT, 2 = LEFT_SEMI,
+ * 3 = LEFT_ANTI (join_kind of include/distributed_join.hpp, which documents
+ * the semantics). LEFT returns left columns then right columns, every
+ * right-hand column with a mask; LEFT_SEMI / LEFT_ANTI return the left
+ * columns only. */
+#define DJ_JOIN_INNER 0
+#define DJ_JOIN_LEFT 1
+#define DJ_JOIN_LEFT_SEMI 2
+#define DJ_JOIN_LEFT_ANTI 3
+void* dj_cpp_distributed_join_ncols_multi(void* comm, int kind, const dj_ncol_desc* lcols,
+                                          int nl, int64_t ln, const dj_ncol_desc* rcols, int nr,
+                                          int64_t rn, const int32_t* lon, const int32_t* ron,
+                                          int nkeys, int over_decom, int report_timing);
+
+/* test/bench hook for the row-marking kernel: sets bit d_idx[i] (row i = bit
+ * i % 32 of uint32 word i / 32) of d_bits for every i < n. The caller zeroes
+ * d_bits and keeps every index inside it; an index may repeat any number of
+ * times. Only words that hold a marked bit are written. mode: -1 = what the
+ * engine runs, else bit 0 = merge lanes naming one word before the atomic,
+ * bit 1 = load the word and skip the atomic when no bit is new (0..3, for
+ * the benchmark's ablation). Runs `reps` times between hipEvent pairs (the
+ * bitmap is NOT re-zeroed in between: repetitions after the first find every
+ * bit set); h_ms (host double[reps], may be NULL) receives the milliseconds.
+ * Synchronizes. */
+void dj_mark_rows(const int64_t* d_idx, int64_t n, void* d_bits, int mode, int reps,
+                  double* h_ms);
+/* test/bench hook for the row-selection kernels: writes to d_out_idx, in
+ * ascending order, the i < nrows whose bit of d_bits equals want_set (bits at
+ * and past nrows are ignored) and returns their number. d_out_idx holds at
+ * least that many int64 (nrows always suffices). Runs `reps` times between
+ * hipEvent pairs; h_ms as above. Synchronizes. */
+int64_t dj_select_rows(const void* d_bits, int64_t nrows, int want_set, int64_t* d_out_idx,
+                       int reps, double* h_ms);
+/* rows one block of dj_select_rows ranks at a time */
+int64_t dj_select_rows_tile_rows(void);
+
 #ifdef __cplusplus
 }
 #endif

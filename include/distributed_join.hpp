@@ -54,3 +54,98 @@ std::unique_ptr<cudf::table> distributed_inner_join(
   bool report_timing               = false,
   void* preallocated_pinned_buffer = nullptr,
   int nvlink_domain_size           = 1);
+
+/* ---- joins that keep left rows without a partner (additions to the
+ * reference's surface; cudf::left_join / left_semi_join / left_anti_join
+ * semantics) ----
+ *
+ * join_kind selects what distributed_join returns on each rank; the
+ * concatenation over ranks is the global result, row order unspecified:
+ *
+ *  INNER      exactly distributed_inner_join (the call is forwarded).
+ *  LEFT       all left columns then all right columns. Every matching pair
+ *             appears as in the inner join; every left row without a match
+ *             appears once with null right-hand cells. EVERY right-hand
+ *             output column carries a validity mask, on every rank, also
+ *             when nothing was unmatched and when the source column had
+ *             none; its null_count is exact (gathered nulls + unmatched
+ *             rows). The values under the padded nulls are zero bytes, the
+ *             padded STRING rows are empty. Left-hand columns have a mask
+ *             exactly when their source had one.
+ *  LEFT_SEMI  the left columns of the left rows that have at least one
+ *             match, each once.
+ *  LEFT_ANTI  the left columns of the left rows that have no match.
+ *
+ * Null keys compare as in the inner join (null_equality::EQUAL): a null left
+ * key is matched exactly when the right side holds a null key in the same
+ * position of the tuple; values stored under a null are never looked at.
+ * An empty left table gives an empty result of the kind's schema; an empty
+ * right table gives LEFT = every left row with an all-null right side,
+ * LEFT_SEMI = empty, LEFT_ANTI = every left row.
+ *
+ * Route: the same validation and inter-domain stage as the inner join, then
+ * both tables are shuffled inside the join group and joined locally — after
+ * the shuffle every right row that could match a left row is on that row's
+ * rank, so no further communication decides matched / unmatched.
+ * over_decom_factor is accepted and has no effect (as for composite keys in
+ * the inner join). Compression options apply to the shuffles. For LEFT_SEMI
+ * and LEFT_ANTI only the right table's key columns are shuffled (with their
+ * compression options); right-hand payload bytes never reach the
+ * communicator. */
+enum class join_kind { INNER, LEFT, LEFT_SEMI, LEFT_ANTI };
+
+std::unique_ptr<cudf::table> distributed_join(
+  join_kind kind,
+  cudf::table_view left,
+  cudf::table_view right,
+  std::vector<cudf::size_type> const& left_on,
+  std::vector<cudf::size_type> const& right_on,
+  Communicator* communicator,
+  std::vector<ColumnCompressionOptions> left_compression_options,
+  std::vector<ColumnCompressionOptions> right_compression_options,
+  int over_decom_factor            = 1,
+  bool report_timing               = false,
+  void* preallocated_pinned_buffer = nullptr,
+  int nvlink_domain_size           = 1);
+
+/* distributed_join(join_kind::LEFT, ...) */
+std::unique_ptr<cudf::table> distributed_left_join(
+  cudf::table_view left,
+  cudf::table_view right,
+  std::vector<cudf::size_type> const& left_on,
+  std::vector<cudf::size_type> const& right_on,
+  Communicator* communicator,
+  std::vector<ColumnCompressionOptions> left_compression_options,
+  std::vector<ColumnCompressionOptions> right_compression_options,
+  int over_decom_factor            = 1,
+  bool report_timing               = false,
+  void* preallocated_pinned_buffer = nullptr,
+  int nvlink_domain_size           = 1);
+
+/* distributed_join(join_kind::LEFT_SEMI, ...) */
+std::unique_ptr<cudf::table> distributed_left_semi_join(
+  cudf::table_view left,
+  cudf::table_view right,
+  std::vector<cudf::size_type> const& left_on,
+  std::vector<cudf::size_type> const& right_on,
+  Communicator* communicator,
+  std::vector<ColumnCompressionOptions> left_compression_options,
+  std::vector<ColumnCompressionOptions> right_compression_options,
+  int over_decom_factor            = 1,
+  bool report_timing               = false,
+  void* preallocated_pinned_buffer = nullptr,
+  int nvlink_domain_size           = 1);
+
+/* distributed_join(join_kind::LEFT_ANTI, ...) */
+std::unique_ptr<cudf::table> distributed_left_anti_join(
+  cudf::table_view left,
+  cudf::table_view right,
+  std::vector<cudf::size_type> const& left_on,
+  std::vector<cudf::size_type> const& right_on,
+  Communicator* communicator,
+  std::vector<ColumnCompressionOptions> left_compression_options,
+  std::vector<ColumnCompressionOptions> right_compression_options,
+  int over_decom_factor            = 1,
+  bool report_timing               = false,
+  void* preallocated_pinned_buffer = nullptr,
+  int nvlink_domain_size           = 1);
