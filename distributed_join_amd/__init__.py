@@ -121,6 +121,7 @@ def lib():
                                                            vp, vp, i32, i32, i32], vp),
             "dj_cpp_shuffle_on_ncols": ([vp, vp, i32, i64, vp, i32, i32, u32, i32], vp),
             "dj_cpp_partition_ncols": ([vp, i32, i64, vp, i32, i32, i32, u32, vp], vp),
+            "dj_cpp_concat_tables": ([vp, i32], vp),
             "dj_table_column_null_mask": ([vp, i32], vp),
             "dj_table_column_null_count": ([vp, i32], i64),
             "dj_gather_bitmasks": ([vp, vp, i32, vp, i64, vp, i32, vp, i32], None),
@@ -130,6 +131,7 @@ def lib():
             "dj_mark_rows": ([vp, i64, vp, i32, i32, vp], None),
             "dj_select_rows": ([vp, i64, i32, vp, i32, vp], i64),
             "dj_select_rows_tile_rows": ([], i64),
+            "dj_grid_span": ([i32, c.POINTER(i64), c.POINTER(i64)], i32),
         }
         for name, (argtypes, restype) in sigs.items():
             f = getattr(_lib, name)
@@ -674,6 +676,33 @@ def cpp_partition_ncols(cols, n, on, nparts, hash_fn=HASH_MURMUR3, seed=0):
     return table_to_numpy_nullable(t), offsets
 
 
+def cpp_concat_ncols(parts):
+    """The concatenation step of the batched join pipeline alone (test hook):
+    parts is a list of (nullable column descriptors, n) tables of one schema.
+    Each part becomes an engine-owned table (a 1-partition placement on its
+    column 0, which leaves the rows where they are) and the tables are
+    concatenated. Returns (cols, masks) as table_to_numpy_nullable."""
+    L = lib()
+    tables = (ctypes.c_void_p * len(parts))()
+    on = np.zeros(1, dtype=np.int32)
+    offsets = np.zeros(2, dtype=np.int64)
+    made = 0
+    try:
+        for i, (cols, n) in enumerate(parts):
+            arr = _pack_ncols(cols)
+            tables[i] = L.dj_cpp_partition_ncols(ctypes.cast(arr, ctypes.c_void_p), len(cols),
+                                                 n, on.ctypes.data, 1, 1, HASH_MURMUR3, 0,
+                                                 offsets.ctypes.data)
+            made += 1
+    except BaseException:
+        # the concatenation never took ownership: free the tables made so far
+        for i in range(made):
+            L.dj_table_free(tables[i])
+        raise
+    t = L.dj_cpp_concat_tables(ctypes.cast(tables, ctypes.c_void_p), len(parts))
+    return table_to_numpy_nullable(t)
+
+
 def gather_bitmasks(src_masks, d_idx_ptr, n, reps=1, cols_per_launch=0):
     """The mask gather kernel through its test/bench hook. src_masks: device
     mask pointers (or None = all valid), one per column; cols_per_launch
@@ -775,6 +804,26 @@ def select_rows(d_bits_ptr, nrows, want_set, d_out_ptr, reps=1):
 def select_rows_tile_rows():
     """Rows one block of select_rows ranks at a time."""
     return int(lib().dj_select_rows_tile_rows())
+
+
+# kernel families of dj_grid_span (DJ_SPAN_* of include/distributed_join.h)
+SPAN_FAMILIES = {
+    "mask_gather": 0, "mask_words": 1, "mark_rows": 2, "select_rows": 3,
+    "gather_fused": 4, "gather_column": 5, "string_rows": 6, "string_sum": 7,
+    "string_scan": 8, "string_hash": 9, "codec_elems": 10, "codec_pack": 11,
+    "key_helpers": 12,
+}
+
+
+def grid_span(family):
+    """(items one full grid of the family's kernels covers in one trip of
+    their grid-stride loops, items one pass of its single-block scan covers or
+    0), from the constants the launchers use. Needs no GPU."""
+    trip, scan = ctypes.c_int64(), ctypes.c_int64()
+    rc = lib().dj_grid_span(SPAN_FAMILIES[family], ctypes.byref(trip), ctypes.byref(scan))
+    if rc != 0:
+        raise ValueError(f"dj_grid_span: unknown family {family!r}")
+    return int(trip.value), int(scan.value)
 
 
 GATHER_FUSED, GATHER_PER_COLUMN, GATHER_AUTO = 0, 1, 2

@@ -25,6 +25,8 @@ namespace {
 
 constexpr int kMaskBlock = 256;
 constexpr int kWave = 64;
+/* blocks per launch at most; a grid-stride loop covers the rest */
+constexpr int kMaskGridCap = 2048;
 
 /* One wave owns 64 consecutive, 64-aligned output rows: lane l tests the
  * source bit of row chunk*64+l, one __ballot per column yields the two mask
@@ -149,12 +151,23 @@ __global__ __launch_bounds__(kMaskBlock) void count_unset_bits_kernel(
 int mask_grid(int64_t items_per_thread_domain)
 {
   int64_t blocks = (items_per_thread_domain + kMaskBlock - 1) / kMaskBlock;
-  if (blocks > 2048) blocks = 2048;
+  if (blocks > kMaskGridCap) blocks = kMaskGridCap;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
 }
 
 }  // namespace
+
+GridSpan bitmask_grid_span(int family)
+{
+  switch (family) {
+    case kSpanMaskGather: /* a wave per 64-row chunk */
+      return {(int64_t)kMaskGridCap * (kMaskBlock / kWave) * kWave, 0};
+    case kSpanMaskWords: /* a thread per mask word */
+      return {(int64_t)kMaskGridCap * kMaskBlock, 0};
+    default: return {0, 0};
+  }
+}
 
 void gather_bitmasks(const BitmaskGatherDesc& desc, const int64_t* d_idx, int64_t n,
                      uint32_t* d_null_counts, hipStream_t s, int cols_per_launch)
@@ -175,7 +188,8 @@ void gather_bitmasks(const BitmaskGatherDesc& desc, const int64_t* d_idx, int64_
       part.src[c] = desc.src[c0 + c];
       part.dst[c] = desc.dst[c0 + c];
     }
-    hipLaunchKernelGGL(gather_bitmasks_kernel, dim3((int)(blocks < 2048 ? blocks : 2048)),
+    hipLaunchKernelGGL(gather_bitmasks_kernel,
+                       dim3((int)(blocks < kMaskGridCap ? blocks : kMaskGridCap)),
                        dim3(kMaskBlock), 0, s, part, d_idx, n, nchunks, d_null_counts + c0);
     DJ_HIP_CALL(hipGetLastError());
   }

@@ -694,4 +694,35 @@ int64_t dj_compress_roundtrip(const void* d_in, int64_t count, int elem_size, in
   return wire;
 }
 
+/* test hook: spans of the capped-grid helper kernels (include/distributed_join.h).
+ * Every file answers for its own families from its launchers' constants. */
+int dj_grid_span(int family, int64_t* trip_items, int64_t* scan_pass_items)
+{
+  static_assert(DJ_SPAN_MASK_GATHER == dj::kSpanMaskGather &&
+                  DJ_SPAN_MASK_WORDS == dj::kSpanMaskWords &&
+                  DJ_SPAN_MARK_ROWS == dj::kSpanMarkRows &&
+                  DJ_SPAN_SELECT_ROWS == dj::kSpanSelectRows &&
+                  DJ_SPAN_GATHER_FUSED == dj::kSpanGatherFused &&
+                  DJ_SPAN_GATHER_COLUMN == dj::kSpanGatherColumn &&
+                  DJ_SPAN_STRING_ROWS == dj::kSpanStringRows &&
+                  DJ_SPAN_STRING_SUM == dj::kSpanStringSum &&
+                  DJ_SPAN_STRING_SCAN == dj::kSpanStringScan &&
+                  DJ_SPAN_STRING_HASH == dj::kSpanStringHash &&
+                  DJ_SPAN_CODEC_ELEMS == dj::kSpanCodecElems &&
+                  DJ_SPAN_CODEC_PACK == dj::kSpanCodecPack &&
+                  DJ_SPAN_KEY_HELPERS == dj::kSpanKeyHelpers &&
+                  DJ_SPAN_FAMILIES == dj::kSpanFamilies,
+                "DJ_SPAN_* of the C ABI and kSpan* of dj_kernels.hpp are one list");
+  const dj::GridSpan all[] = {dj::bitmask_grid_span(family),  dj::rowset_grid_span(family),
+                              dj::gather_grid_span(family),   dj::strings_grid_span(family),
+                              dj::compress_grid_span(family), dj::key_helper_grid_span(family)};
+  dj::GridSpan span{0, 0};
+  for (const dj::GridSpan& s : all)
+    if (s.trip > 0) span = s;
+  if (span.trip <= 0) return -1;
+  *trip_items = span.trip;
+  *scan_pass_items = span.scan_pass;
+  return 0;
+}
+
 }  // extern "C"

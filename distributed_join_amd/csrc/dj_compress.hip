@@ -62,6 +62,10 @@ struct CompScratch {
 };
 
 constexpr int SCHUNK = 2048;
+/* blocks per launch at most; grid-stride loops cover the rest */
+constexpr int CGRID_CAP = 2048;
+/* chunk partials one pass of scan64_exclusive_kernel (one block) takes */
+constexpr int CSCAN_PASS = 1024;
 
 __host__ __device__ inline CompScratch carve_comp_scratch(void* p, int64_t n)
 {
@@ -80,7 +84,7 @@ __host__ __device__ inline CompScratch carve_comp_scratch(void* p, int64_t n)
 int cgrid(int64_t n)
 {
   int64_t b = (n + CBLOCK - 1) / CBLOCK;
-  if (b > 2048) b = 2048;
+  if (b > CGRID_CAP) b = CGRID_CAP;
   if (b < 1) b = 1;
   return (int)b;
 }
@@ -442,16 +446,16 @@ __global__ void scan64_partials_kernel(const int64_t* __restrict__ v, int64_t n,
 
 __global__ void scan64_exclusive_kernel(int64_t* partials, int64_t nchunks)
 {
-  __shared__ int64_t sh[1024];
+  __shared__ int64_t sh[CSCAN_PASS];
   __shared__ int64_t running_sh;
   if (threadIdx.x == 0) running_sh = 0;
   __syncthreads();
-  for (int64_t base = 0; base < nchunks; base += 1024) {
+  for (int64_t base = 0; base < nchunks; base += CSCAN_PASS) {
     int64_t c = base + threadIdx.x;
     int64_t v = (c < nchunks) ? partials[c] : 0;
     sh[threadIdx.x] = v;
     __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
+    for (int off = 1; off < CSCAN_PASS; off <<= 1) {
       int64_t add = (threadIdx.x >= (unsigned)off) ? sh[threadIdx.x - off] : 0;
       __syncthreads();
       sh[threadIdx.x] += add;
@@ -460,7 +464,7 @@ __global__ void scan64_exclusive_kernel(int64_t* partials, int64_t nchunks)
     int64_t rbase = running_sh;
     __syncthreads();
     if (c < nchunks) partials[c] = rbase + sh[threadIdx.x] - v;
-    if (threadIdx.x == 1023) running_sh = rbase + sh[threadIdx.x];
+    if (threadIdx.x == CSCAN_PASS - 1) running_sh = rbase + sh[threadIdx.x];
     __syncthreads();
   }
 }
@@ -524,6 +528,17 @@ __global__ void rle_expand_kernel(const int64_t* __restrict__ vals,
 
 /* ---------------- host launchers ---------------- */
 
+GridSpan compress_grid_span(int family)
+{
+  switch (family) {
+    case kSpanCodecElems: /* a thread per element; a scan partial per SCHUNK values */
+      return {(int64_t)CGRID_CAP * CBLOCK, (int64_t)CSCAN_PASS * SCHUNK};
+    case kSpanCodecPack: /* a thread per group of 32 values */
+      return {(int64_t)CGRID_CAP * CBLOCK * 32, 0};
+    default: return {0, 0};
+  }
+}
+
 size_t compress_bound(int64_t count, int elem_size)
 {
   /* header + worst case raw (+ slack for the last zero-padded pack group) */
@@ -558,7 +573,7 @@ void compress_slice_async(const void* d_in, int64_t count, int elem_size, int nu
     hipLaunchKernelGGL(scan64_partials_kernel, dim3(cgrid(nchunks)), dim3(CBLOCK), 0, s,
                        scr.marks, count, nchunks, scr.partials);
     DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(scan64_exclusive_kernel, dim3(1), dim3(1024), 0, s, scr.partials,
+    hipLaunchKernelGGL(scan64_exclusive_kernel, dim3(1), dim3(CSCAN_PASS), 0, s, scr.partials,
                        nchunks);
     DJ_HIP_CALL(hipGetLastError());
     DJ_LAUNCH_BY_ELEM(rle_emit_kernel, elem_size, cgrid(nchunks), s, d_in, count, nchunks,
@@ -637,7 +652,7 @@ void decompress_slice_async(const uint8_t* d_comp, const CompSliceHeader& h, int
     hipLaunchKernelGGL(scan64_partials_kernel, dim3(cgrid(rchunks)), dim3(CBLOCK), 0, s,
                        scr.marks, r, rchunks, scr.partials);
     DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(scan64_exclusive_kernel, dim3(1), dim3(1024), 0, s, scr.partials,
+    hipLaunchKernelGGL(scan64_exclusive_kernel, dim3(1), dim3(CSCAN_PASS), 0, s, scr.partials,
                        rchunks);
     DJ_HIP_CALL(hipGetLastError());
     hipLaunchKernelGGL(scan64_excl_finalize_kernel, dim3(cgrid(rchunks)), dim3(CBLOCK), 0, s,
@@ -651,8 +666,8 @@ void decompress_slice_async(const uint8_t* d_comp, const CompSliceHeader& h, int
       hipLaunchKernelGGL(scan64_partials_kernel, dim3(cgrid(rchunks)), dim3(CBLOCK), 0, s,
                          scr.vals, r, rchunks, scr.partials);
       DJ_HIP_CALL(hipGetLastError());
-      hipLaunchKernelGGL(scan64_exclusive_kernel, dim3(1), dim3(1024), 0, s, scr.partials,
-                         rchunks);
+      hipLaunchKernelGGL(scan64_exclusive_kernel, dim3(1), dim3(CSCAN_PASS), 0, s,
+                         scr.partials, rchunks);
       DJ_HIP_CALL(hipGetLastError());
       hipLaunchKernelGGL((scan64_finalize_kernel<int64_t>), dim3(cgrid(rchunks)),
                          dim3(CBLOCK), 0, s, scr.vals, r, rchunks, scr.partials, scr.vals);
@@ -673,7 +688,8 @@ void decompress_slice_async(const uint8_t* d_comp, const CompSliceHeader& h, int
     hipLaunchKernelGGL(scan64_partials_kernel, dim3(cgrid(nchunks)), dim3(CBLOCK), 0, s, vals,
                        n, nchunks, partials);
     DJ_HIP_CALL(hipGetLastError());
-    hipLaunchKernelGGL(scan64_exclusive_kernel, dim3(1), dim3(1024), 0, s, partials, nchunks);
+    hipLaunchKernelGGL(scan64_exclusive_kernel, dim3(1), dim3(CSCAN_PASS), 0, s, partials,
+                       nchunks);
     DJ_HIP_CALL(hipGetLastError());
     DJ_LAUNCH_BY_ELEM(scan64_finalize_kernel, elem_size, cgrid(nchunks), s, vals, n, nchunks,
                       partials, d_out);

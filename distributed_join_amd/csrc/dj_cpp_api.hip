@@ -40,11 +40,13 @@
 namespace {
 
 constexpr int kBlock = 256;
+/* blocks per launch at most; a grid-stride loop covers the rest */
+constexpr int kGridCap = 2048;
 
 int grid_for_n(int64_t n)
 {
   int64_t blocks = (n + kBlock - 1) / kBlock;
-  if (blocks > 2048) blocks = 2048;
+  if (blocks > kGridCap) blocks = kGridCap;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
 }
@@ -503,6 +505,13 @@ class LocalCommunicator : public Communicator {
 };
 
 }  // namespace
+
+/* this file's row kernels (grid_for_n): a thread per row (dj_kernels.hpp) */
+dj::GridSpan dj::key_helper_grid_span(int family)
+{
+  if (family == dj::kSpanKeyHelpers) return {(int64_t)kGridCap * kBlock, 0};
+  return {0, 0};
+}
 
 /* --------------------------------------------------------- cudf::column */
 
@@ -3277,6 +3286,19 @@ void* dj_cpp_partition_ncols(const dj_ncol_desc* cols, int nc, int64_t n, const 
                hash_function == DJ_HASH_IDENTITY ? DJ_HASH_IDENTITY : DJ_HASH_MURMUR3, seed);
   for (int i = 0; i <= nparts; i++) h_offsets[i] = part.offsets[(size_t)i];
   return part.tbl.release();
+}
+
+/* test hook: concat_tables, the step that joins the batches of the batched
+ * pipeline into one result (a STRING column's offsets are rebased part by
+ * part, masks concatenate bit-exactly). A single-rank join never has more
+ * than one part, so only this hook reaches the step without a second rank.
+ * Takes ownership of the n >= 1 input tables. */
+void* dj_cpp_concat_tables(void* const* tables, int n)
+{
+  DJ_CHECK_ERROR(n >= 1, "concat: at least one table");
+  std::vector<std::unique_ptr<cudf::table>> parts;
+  for (int i = 0; i < n; i++) parts.emplace_back((cudf::table*)tables[i]);
+  return concat_tables(parts).release();
 }
 
 const void* dj_table_column_null_mask(void* tbl, int i)

@@ -65,10 +65,12 @@ __global__ void fill_i64_kernel(int64_t* dst, int64_t value, int64_t n)
   for (; i < n; i += stride) dst[i] = value;
 }
 
+constexpr int kGridCap = 2048;  // 256 CU x 8 blocks, grid-stride the rest
+
 static int grid_for(int64_t n)
 {
   int64_t blocks = (n + BLOCK - 1) / BLOCK;
-  if (blocks > 2048) blocks = 2048;  // 256 CU x 8 blocks, grid-stride the rest
+  if (blocks > kGridCap) blocks = kGridCap;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
 }
@@ -331,6 +333,17 @@ void gather_table(const GatherCol* cols, int ncols, const int64_t* d_idx, int64_
     }
   }
   if (d.ncols > 0) launch_gather_fused(d, d_idx, n, s);
+}
+
+GridSpan gather_grid_span(int family)
+{
+  switch (family) {
+    case kSpanGatherFused: /* a thread per four rows */
+      return {(int64_t)kGridCap * BLOCK * 4, 0};
+    case kSpanGatherColumn: /* a thread per row */
+      return {(int64_t)kGridCap * BLOCK, 0};
+    default: return {0, 0};
+  }
 }
 
 /* ------------------------------------------------------------- generator */

@@ -364,6 +364,46 @@ void select_rows(const uint32_t* d_bits, int64_t nrows, bool want_set, int64_t* 
 /* rows one block of select_rows ranks at a time (tests probe around it) */
 int64_t select_rows_tile_rows();
 
+/* ----- test hook: what one launch of a capped-grid helper kernel covers -----
+ * Every helper kernel outside the bucket-join core runs on a grid capped at a
+ * few thousand blocks and takes the rest of its input in further trips of a
+ * grid-stride loop; the scans behind them turn per-tile partials into offsets
+ * in one block, in passes. `trip` is the number of items (rows, words, groups
+ * x 32 values — the unit the family's callers size by) one full grid covers
+ * in one trip, `scan_pass` the number of items whose partials one pass of the
+ * single-block scan covers (0: the family has no such scan). Each file answers
+ * for its own families from the constants its launchers use, and returns
+ * {0, 0} for a family of another file. Tests size their inputs from these. */
+struct GridSpan {
+  int64_t trip;
+  int64_t scan_pass;
+};
+enum {
+  kSpanMaskGather = 0,   /* gather_bitmasks: rows */
+  kSpanMaskWords = 1,    /* copy_bitmask_segments, count_unset_bits: mask words */
+  kSpanMarkRows = 2,     /* mark_rows: indices */
+  kSpanSelectRows = 3,   /* select_rows: rows; scan_pass: tile_scan with chunk 1 */
+  kSpanGatherFused = 4,  /* gather_table, fused kernel: rows */
+  kSpanGatherColumn = 5, /* gather_table, per-column kernel: rows */
+  kSpanStringRows = 6,   /* sizes_from_offsets, gather_sizes_starts,
+                            gather_chars_from_starts, filter_tuple_matches_mixed */
+  kSpanStringSum = 7,    /* sum_sizes_i64: rows */
+  kSpanStringScan = 8,   /* offsets_from_sizes: rows */
+  kSpanStringHash = 9,   /* hash_strings: rows */
+  kSpanCodecElems = 10,  /* codec element loops: elements; scan_pass: values of
+                            scan64_exclusive */
+  kSpanCodecPack = 11,   /* codec pack loops: values (32 per group) */
+  kSpanKeyHelpers = 12,  /* widen_key, narrow_key, fuse_keys, nullable_key_hash,
+                            rebase_offsets (dj_cpp_api.hip): rows */
+  kSpanFamilies = 13
+};
+GridSpan bitmask_grid_span(int family);
+GridSpan rowset_grid_span(int family);
+GridSpan gather_grid_span(int family);
+GridSpan strings_grid_span(int family);
+GridSpan compress_grid_span(int family);
+GridSpan key_helper_grid_span(int family); /* dj_cpp_api.hip */
+
 /* ----- small utilities ----- */
 void fill_i64(int64_t* d_dst, int64_t value, int64_t n, hipStream_t s);
 /* out-of-band join of rows whose key equals the reserved empty sentinel

@@ -23,6 +23,8 @@ namespace {
 
 constexpr int kRowsetBlock = 256;
 constexpr int kWave = 64;
+/* blocks per launch at most; a grid-stride loop covers the rest */
+constexpr int kRowsetGridCap = 4096;
 
 /* ------------------------------------------------------------- mark_rows
  *
@@ -212,7 +214,7 @@ template <int MODE>
 void launch_mark(const int64_t* d_idx, int64_t n, uint32_t* d_bits, hipStream_t s)
 {
   int64_t blocks = (n + kRowsetBlock - 1) / kRowsetBlock;
-  if (blocks > 4096) blocks = 4096;
+  if (blocks > kRowsetGridCap) blocks = kRowsetGridCap;
   hipLaunchKernelGGL(mark_rows_kernel<MODE>, dim3((int)blocks), dim3(kRowsetBlock), 0, s, d_idx,
                      n, d_bits);
   DJ_HIP_CALL(hipGetLastError());
@@ -235,6 +237,17 @@ void mark_rows(const int64_t* d_idx, int64_t n, uint32_t* d_bits, hipStream_t s,
 
 int64_t select_rows_tile_rows() { return kTileRows; }
 
+GridSpan rowset_grid_span(int family)
+{
+  switch (family) {
+    case kSpanMarkRows: /* a thread per index */
+      return {(int64_t)kRowsetGridCap * kRowsetBlock, 0};
+    case kSpanSelectRows: /* a block per tile; tile_scan's chunk is 1 up to kScanBlock tiles */
+      return {(int64_t)kRowsetGridCap * kTileRows, (int64_t)kScanBlock * kTileRows};
+    default: return {0, 0};
+  }
+}
+
 size_t select_rows_scratch_bytes(int64_t nrows)
 {
   const int64_t ntiles = select_tiles(nrows > 0 ? nrows : 0);
@@ -252,7 +265,7 @@ void select_rows(const uint32_t* d_bits, int64_t nrows, bool want_set, int64_t* 
   DJ_CHECK_ERROR(d_bits != nullptr && d_out_idx != nullptr && d_scratch != nullptr,
                  "select_rows: null pointer");
   const int64_t ntiles = select_tiles(nrows);
-  const int grid = (int)(ntiles < 4096 ? ntiles : 4096);
+  const int grid = (int)(ntiles < kRowsetGridCap ? ntiles : kRowsetGridCap);
   int64_t* tiles = (int64_t*)d_scratch;
   hipLaunchKernelGGL(tile_count_kernel, dim3(grid), dim3(kRowsetBlock), 0, s, d_bits, nrows,
                      ntiles, want_set, tiles);

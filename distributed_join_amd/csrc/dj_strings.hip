@@ -33,11 +33,16 @@ namespace {
 constexpr int SBLOCK = 256;
 constexpr int SVPT = 8;  // elements per thread in the scan partials pass
 constexpr int CHUNK = SBLOCK * SVPT;
+/* blocks per launch at most; grid-stride loops cover the rest */
+constexpr int SGRID_CAP = 2048;      // row loops and the scan's tile loops
+constexpr int SUM_GRID_CAP = 1024;   // sum_sizes_i64
+constexpr int HS_GRID_CAP = 4096;    // hash_strings
+constexpr int SCAN_PASS = 1024;      // partials one pass of the single-block scan takes
 
 int sgrid(int64_t n)
 {
   int64_t b = (n + SBLOCK - 1) / SBLOCK;
-  if (b > 2048) b = 2048;
+  if (b > SGRID_CAP) b = SGRID_CAP;
   if (b < 1) b = 1;
   return (int)b;
 }
@@ -71,7 +76,7 @@ __global__ void sum_sizes_i64_kernel(const int32_t* __restrict__ sizes, int64_t 
 void sum_sizes_i64(const int32_t* d_sizes, int64_t n, int64_t* d_total, hipStream_t s)
 {
   int64_t b = (n + 255) / 256;
-  if (b > 1024) b = 1024;
+  if (b > SUM_GRID_CAP) b = SUM_GRID_CAP;
   if (b < 1) b = 1;
   hipLaunchKernelGGL(sum_sizes_i64_kernel, dim3((uint32_t)b), dim3(256), 0, s, d_sizes, n,
                      d_total);
@@ -173,16 +178,16 @@ __global__ void scan_tile_finalize_kernel(const int32_t* __restrict__ sizes, int
 /* single block: exclusive scan of partials in place */
 __global__ void scan_partials_exclusive_kernel(int64_t* partials, int64_t nchunks)
 {
-  __shared__ int64_t sh[1024];
+  __shared__ int64_t sh[SCAN_PASS];
   __shared__ int64_t running_sh;
   if (threadIdx.x == 0) running_sh = 0;
   __syncthreads();
-  for (int64_t base = 0; base < nchunks; base += 1024) {
+  for (int64_t base = 0; base < nchunks; base += SCAN_PASS) {
     int64_t c = base + threadIdx.x;
     int64_t v = (c < nchunks) ? partials[c] : 0;
     sh[threadIdx.x] = v;
     __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
+    for (int off = 1; off < SCAN_PASS; off <<= 1) {
       int64_t add = (threadIdx.x >= (unsigned)off) ? sh[threadIdx.x - off] : 0;
       __syncthreads();
       sh[threadIdx.x] += add;
@@ -191,7 +196,7 @@ __global__ void scan_partials_exclusive_kernel(int64_t* partials, int64_t nchunk
     int64_t rbase = running_sh;
     __syncthreads();
     if (c < nchunks) partials[c] = rbase + sh[threadIdx.x] - v;
-    if (threadIdx.x == 1023) running_sh = rbase + sh[threadIdx.x];
+    if (threadIdx.x == SCAN_PASS - 1) running_sh = rbase + sh[threadIdx.x];
     __syncthreads();
   }
 }
@@ -211,11 +216,11 @@ void offsets_from_sizes(const int32_t* d_sizes, int64_t n, int32_t* d_offsets, v
   }
   int64_t* partials = (int64_t*)d_scratch;  // scratch sized by CHUNK < SCAN_T
   int64_t ntiles = (n + SCAN_T - 1) / SCAN_T;
-  int tgrid = (int)(ntiles < 2048 ? ntiles : 2048);
+  int tgrid = (int)(ntiles < SGRID_CAP ? ntiles : SGRID_CAP);
   hipLaunchKernelGGL(scan_tile_partials_kernel, dim3(tgrid), dim3(SBLOCK), 0, s, d_sizes, n,
                      ntiles, partials);
   DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(scan_partials_exclusive_kernel, dim3(1), dim3(1024), 0, s, partials,
+  hipLaunchKernelGGL(scan_partials_exclusive_kernel, dim3(1), dim3(SCAN_PASS), 0, s, partials,
                      ntiles);
   DJ_HIP_CALL(hipGetLastError());
   hipLaunchKernelGGL(scan_tile_finalize_kernel, dim3(tgrid), dim3(SBLOCK), 0, s, d_sizes, n,
@@ -510,7 +515,7 @@ void launch_hash_strings(const int32_t* d_offsets, const uint8_t* d_chars, int64
   /* A/B switch for the staged path (benchmark/string_key_bench.py) */
   static const int force_direct = getenv("DJ_STRHASH_FORCE_DIRECT") ? 1 : 0;
   const int64_t ntiles = (n + HS_TILE_ROWS - 1) / HS_TILE_ROWS;
-  const int grid = (int)(ntiles < 4096 ? ntiles : 4096);
+  const int grid = (int)(ntiles < HS_GRID_CAP ? ntiles : HS_GRID_CAP);
   hipLaunchKernelGGL(hash_strings_kernel, dim3(grid), dim3(HS_BLOCK), 0, s, d_offsets, d_chars,
                      n, ntiles, force_direct, seed_a, seed_b, d_out64, d_out32);
   DJ_HIP_CALL(hipGetLastError());
@@ -528,6 +533,18 @@ void hash_strings_seeded(const int32_t* d_offsets, const uint8_t* d_chars, int64
                          uint32_t seed, uint32_t* d_out, hipStream_t s)
 {
   launch_hash_strings(d_offsets, d_chars, n, seed, seed, nullptr, d_out, s);
+}
+
+GridSpan strings_grid_span(int family)
+{
+  switch (family) {
+    case kSpanStringRows: return {(int64_t)SGRID_CAP * SBLOCK, 0};
+    case kSpanStringSum: return {(int64_t)SUM_GRID_CAP * 256, 0};
+    case kSpanStringScan: /* a block per SCAN_T-row tile, a partial per tile */
+      return {(int64_t)SGRID_CAP * SCAN_T, (int64_t)SCAN_PASS * SCAN_T};
+    case kSpanStringHash: return {(int64_t)HS_GRID_CAP * HS_TILE_ROWS, 0};
+    default: return {0, 0};
+  }
 }
 
 /* ---- collision filter over key tuples: integer-rep and STRING columns ---- */

@@ -260,6 +260,11 @@ void* dj_cpp_shuffle_on_ncols(void* comm, const dj_ncol_desc* cols, int nc, int6
 void* dj_cpp_partition_ncols(const dj_ncol_desc* cols, int nc, int64_t n, const int32_t* on,
                              int nkeys, int nparts, int hash_function, uint32_t seed,
                              int64_t* h_offsets);
+/* test hook: the concatenation step of the batched join pipeline alone — the
+ * rows of the n >= 1 opaque tables (same schema) back to back; STRING offsets
+ * are rebased part by part, masks concatenated (a part without one counts as
+ * all valid). Takes ownership of the input tables: free only the result. */
+void* dj_cpp_concat_tables(void* const* tables, int n);
 /* mask (device pointer, NULL when the column has none) and exact null count
  * of column i of an opaque table */
 const void* dj_table_column_null_mask(void* tbl, int i);
@@ -322,6 +327,35 @@ int64_t dj_select_rows(const void* d_bits, int64_t nrows, int want_set, int64_t*
                        int reps, double* h_ms);
 /* rows one block of dj_select_rows ranks at a time */
 int64_t dj_select_rows_tile_rows(void);
+
+/* ---------------- test hook: spans of the capped-grid helper kernels.
+ * Every helper kernel outside the bucket-join core is launched on a grid
+ * capped at a few thousand blocks and covers the rest of its input in further
+ * trips of a grid-stride loop; the scans behind them turn per-tile partials
+ * into offsets in one block, in passes. For a kernel family, *trip_items is
+ * the number of items (the unit named below) one full grid covers in one
+ * trip and *scan_pass_items the number of items one pass of the single-block
+ * scan covers (0: the family has no such scan). Both are computed from the
+ * constants the launchers use, so tests that size their inputs from them
+ * follow a changed cap. Returns 0, or -1 for an unknown family. */
+#define DJ_SPAN_MASK_GATHER 0    /* gather_bitmasks: rows */
+#define DJ_SPAN_MASK_WORDS 1     /* copy_bitmask_segments, count_unset_bits: 32-bit words */
+#define DJ_SPAN_MARK_ROWS 2      /* mark_rows: indices */
+#define DJ_SPAN_SELECT_ROWS 3    /* select_rows: rows; scan: tile_scan with a chunk of 1 */
+#define DJ_SPAN_GATHER_FUSED 4   /* table gather, fused kernel: rows */
+#define DJ_SPAN_GATHER_COLUMN 5  /* table gather, per-column kernel: rows */
+#define DJ_SPAN_STRING_ROWS 6    /* sizes_from_offsets, gather_sizes_starts,
+                                    gather_chars_from_starts, tuple filter: rows */
+#define DJ_SPAN_STRING_SUM 7     /* sum_sizes_i64: rows */
+#define DJ_SPAN_STRING_SCAN 8    /* offsets_from_sizes: rows */
+#define DJ_SPAN_STRING_HASH 9    /* hash_strings: rows */
+#define DJ_SPAN_CODEC_ELEMS 10   /* cascaded codec element loops: elements; scan:
+                                    values of its chunked int64 scan */
+#define DJ_SPAN_CODEC_PACK 11    /* cascaded codec pack loops: values (32 a group) */
+#define DJ_SPAN_KEY_HELPERS 12   /* widen_key, narrow_key, fuse_keys,
+                                    nullable_key_hash, rebase_offsets: rows */
+#define DJ_SPAN_FAMILIES 13
+int dj_grid_span(int family, int64_t* trip_items, int64_t* scan_pass_items);
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,45 @@ def test_device_count_callable_without_gpu():
     assert n >= 0  # 0 in this container
 
 
+# family -> (items one full grid covers in one trip, items one pass of the
+# single-block scan covers or 0). tests/test_gpu_second_trip.py sizes its
+# inputs from dj_grid_span, so its tests follow a changed cap; this table makes
+# such a change a visible, deliberate edit.
+GRID_SPANS = {
+    "mask_gather": (524_288, 0),
+    "mask_words": (524_288, 0),            # = 16,777,216 bits
+    "mark_rows": (1_048_576, 0),
+    "select_rows": (33_554_432, 8_388_608),
+    "gather_fused": (2_097_152, 0),
+    "gather_column": (524_288, 0),
+    "string_rows": (524_288, 0),
+    "string_sum": (262_144, 0),
+    "string_scan": (8_388_608, 4_194_304),
+    "string_hash": (8_388_608, 0),
+    "codec_elems": (524_288, 2_097_152),
+    "codec_pack": (16_777_216, 0),
+    "key_helpers": (524_288, 0),
+}
+
+
+def test_grid_span_hook_matches_the_recorded_caps():
+    _build()
+    import distributed_join_amd as dj
+    assert set(dj.SPAN_FAMILIES) == set(GRID_SPANS)
+    assert sorted(dj.SPAN_FAMILIES.values()) == list(range(len(GRID_SPANS)))
+    # the Python numbering is the header's, name by name (several families
+    # share a span, so the values alone would not show two of them swapped)
+    defines = dict(re.findall(r"#define\s+DJ_SPAN_(\w+)\s+(\d+)", open(HEADER).read()))
+    assert int(defines.pop("FAMILIES")) == len(GRID_SPANS)
+    assert {k.lower(): int(v) for k, v in defines.items()} == dj.SPAN_FAMILIES
+    for family, want in GRID_SPANS.items():
+        assert dj.grid_span(family) == want, family
+    trip, scan = ctypes.c_int64(-1), ctypes.c_int64(-1)
+    for unknown in (-1, len(GRID_SPANS)):
+        assert dj.lib().dj_grid_span(unknown, ctypes.byref(trip), ctypes.byref(scan)) == -1
+        assert trip.value == -1 and scan.value == -1
+
+
 def test_product_path_fails_loudly_without_gpu():
     _build()
     import distributed_join_amd as dj
