@@ -831,6 +831,12 @@ constexpr int BUCKET_THREADS = 1024;
 constexpr int JOIN_LDS_SLOTS = 2048;        // 32 KiB of longlong2 pairs
 constexpr int JOIN_STAGE_ROWS = 1024;       // 32 KiB staged output rows (4 x i64)
 /* table + stage = 64 KiB + 16 B -> 2 blocks/CU */
+/* lds_join_kernel: staged rows at which a bucket before the group's last one
+ * flushes early; buckets per flush group (the KBUK contract); grid cap in
+ * groups — a block takes further groups in further trips */
+constexpr int JOIN_STAGE_WATERMARK = JOIN_STAGE_ROWS - JOIN_STAGE_ROWS / 4;
+constexpr int JOIN_FLUSH_GROUP = 4;
+constexpr int JOIN_GRID_GROUPS = 8192;
 constexpr int SUB_BUCKETS = 256;            // pass-B fanout (fixed)
 
 int bucket_count_for(int64_t ln, int64_t rn)
@@ -1302,7 +1308,7 @@ __global__ __launch_bounds__(BUCKET_THREADS) void lds_join_kernel(
   int* __restrict__ error)
 {
   constexpr int S = JOIN_STAGE_ROWS;
-  constexpr int WATER = S - S / 4;
+  constexpr int WATER = JOIN_STAGE_WATERMARK;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   longlong2* tbl = (longlong2*)smem;
   int64_t* stage = (int64_t*)(tbl + SLOTS2);  // SoA: stage[c*JOIN_STAGE_ROWS + i]
@@ -1907,8 +1913,8 @@ static void lds_join_launch(const longlong2* d_lrows, const int64_t* d_loff,
   DJ_CHECK_ERROR(table_slots == 2048 || table_slots == 4096,
                  "lds_join: table_slots must be 2048 or 4096");
   const bool slack = d_llen != nullptr;
-  const int64_t groups = (int64_t)B / 4;
-  int grid = (int)(groups < 8192 ? groups : 8192);
+  const int64_t groups = (int64_t)B / JOIN_FLUSH_GROUP;
+  int grid = (int)(groups < JOIN_GRID_GROUPS ? groups : JOIN_GRID_GROUPS);
   size_t lds =
     (size_t)table_slots * sizeof(longlong2) + 4 * JOIN_STAGE_ROWS * sizeof(int64_t) + 16;
   auto launch = [&](auto kern) {
@@ -1917,9 +1923,16 @@ static void lds_join_launch(const longlong2* d_lrows, const int64_t* d_loff,
               (unsigned long long*)d_counter, d_overflow_flags, d_any_overflow, d_error);
   };
   if (table_slots == 4096)
-    slack ? launch(lds_join_kernel<4096, true, 4>) : launch(lds_join_kernel<4096, false, 4>);
+    slack ? launch(lds_join_kernel<4096, true, JOIN_FLUSH_GROUP>)
+          : launch(lds_join_kernel<4096, false, JOIN_FLUSH_GROUP>);
   else
-    slack ? launch(lds_join_kernel<2048, true, 4>) : launch(lds_join_kernel<2048, false, 4>);
+    slack ? launch(lds_join_kernel<2048, true, JOIN_FLUSH_GROUP>)
+          : launch(lds_join_kernel<2048, false, JOIN_FLUSH_GROUP>);
+}
+
+LdsJoinShape lds_join_shape()
+{
+  return {JOIN_STAGE_ROWS, JOIN_STAGE_WATERMARK, JOIN_FLUSH_GROUP, JOIN_GRID_GROUPS};
 }
 
 void lds_join(const longlong2* d_lrows, const int64_t* d_loff, const longlong2* d_rrows,
@@ -1927,7 +1940,7 @@ void lds_join(const longlong2* d_lrows, const int64_t* d_loff, const longlong2* 
               int64_t* d_out2, int64_t* d_out3, int64_t cap, int64_t* d_counter,
               uint32_t* d_overflow_flags, int* d_any_overflow, int* d_error, hipStream_t s)
 {
-  DJ_CHECK_ERROR(B % 4 == 0,
+  DJ_CHECK_ERROR(B % JOIN_FLUSH_GROUP == 0,
                  "lds_join: B must be a multiple of 4 — see lds_join_kernel's KBUK contract");
   lds_join_launch(d_lrows, d_loff, nullptr, 0, d_rrows, d_roff, nullptr, 0, B, table_slots,
                   d_out0, d_out1, d_out2, d_out3, cap, d_counter, d_overflow_flags,
@@ -1941,7 +1954,7 @@ void lds_join_slack(const longlong2* d_lrows, const uint32_t* d_llen, int64_t ca
                     uint32_t* d_overflow_flags, int* d_any_overflow, int* d_error,
                     hipStream_t s)
 {
-  DJ_CHECK_ERROR(B % 4 == 0,
+  DJ_CHECK_ERROR(B % JOIN_FLUSH_GROUP == 0,
                  "lds_join_slack: B must be padded to a multiple of 4 (zero-length "
                  "buckets) — see lds_join_kernel's KBUK contract");
   lds_join_launch(d_lrows, nullptr, d_llen, capL, d_rrows, nullptr, d_rlen, capR, B,

@@ -166,6 +166,14 @@ void lds_join_slack(const longlong2* d_lrows, const uint32_t* d_llen, int64_t ca
                     int64_t* d_out3, int64_t cap, int64_t* d_counter,
                     uint32_t* d_overflow_flags, int* d_any_overflow, int* d_error,
                     hipStream_t s);
+/* lds_join_kernel's shape (tests size their buckets from it): rows of the
+ * LDS output stage; the staged-row count at which a bucket before its group's
+ * last one flushes early; buckets per flush group; the grid cap in groups (a
+ * block takes group blockIdx.x + k * grid_groups in its trip k). */
+struct LdsJoinShape {
+  int stage_rows, watermark, flush_group, grid_groups;
+};
+LdsJoinShape lds_join_shape();
 /* Global-table build/probe over interleaved pair inputs (skew fallback). */
 void join_build_pairs(const longlong2* d_rows, int64_t ln, int64_t* d_table, int64_t nslots,
                       int* d_error, hipStream_t s);
