@@ -1935,6 +1935,11 @@ LdsJoinShape lds_join_shape()
   return {JOIN_STAGE_ROWS, JOIN_STAGE_WATERMARK, JOIN_FLUSH_GROUP, JOIN_GRID_GROUPS};
 }
 
+BucketPartitionShape bucket_partition_shape()
+{
+  return {SCATTER_TILE, SLACK_TILE, BTILE, BUCKET_BLOCKS, BUCKET_THREADS};
+}
+
 void lds_join(const longlong2* d_lrows, const int64_t* d_loff, const longlong2* d_rrows,
               const int64_t* d_roff, int B, int table_slots, int64_t* d_out0, int64_t* d_out1,
               int64_t* d_out2, int64_t* d_out3, int64_t cap, int64_t* d_counter,

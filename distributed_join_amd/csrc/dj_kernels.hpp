@@ -135,7 +135,16 @@ void bucket_partition2(const int64_t* d_keys, const int64_t* d_pay, int64_t n, i
  * any slack segment sets bit 2 of *d_any_overflow (partition output
  * incomplete -> caller redoes exactly). Requires PA >= 2, n < 2^32,
  * PA*slack_capA(n,PA)+n and B*capB < 2^32 (checked; errors loudly
- * otherwise). */
+ * otherwise).
+ * Contracts the direct tests rely on (tests/cpp/slack_pair_check.cpp):
+ * - capB<t> is ANY caller-chosen per-bucket capacity >= 1 — the layout, the
+ *   limits and the length clamp all derive from the argument; slack_capB(n, B)
+ *   is merely what the product passes. d_out<t> is longlong2[B*capB<t>].
+ * - n0 + n1 >= 1: the pass-A grid split divides by n0 + n1 (either table
+ *   alone may be empty; its lens are then all 0).
+ * - bits already set in *d_any_overflow are kept (the kernels only OR in 2);
+ *   d_cur<t> needs no reset by the caller and reads back min(group count,
+ *   slack_capA) per group. */
 void bucket_partition2_slack_pair(const int64_t* d_k0, const int64_t* d_p0, int64_t n0,
                                   longlong2* d_tmp0, uint32_t* d_cur0, int64_t capB0,
                                   longlong2* d_out0, uint32_t* d_len0, const int64_t* d_k1,
@@ -174,6 +183,15 @@ struct LdsJoinShape {
   int stage_rows, watermark, flush_group, grid_groups;
 };
 LdsJoinShape lds_join_shape();
+/* the partition launchers' shape (tests size their inputs from it): rows of
+ * the staged tile of the counted scatters and pass B over lists
+ * (fused_partition, subpart_lists, bucket_partition2), of the slack pass A and
+ * of the slack pass B; chunking blocks per table of a pass A (the slack pair
+ * launches 2 * bucket_blocks and splits them by table size); block size. */
+struct BucketPartitionShape {
+  int scatter_tile, slack_tile, btile, bucket_blocks, bucket_threads;
+};
+BucketPartitionShape bucket_partition_shape();
 /* Global-table build/probe over interleaved pair inputs (skew fallback). */
 void join_build_pairs(const longlong2* d_rows, int64_t ln, int64_t* d_table, int64_t nslots,
                       int* d_error, hipStream_t s);
