@@ -9,7 +9,8 @@
  *
  * Per run: offsets[0] == 0, offsets[B] == n, offsets non-decreasing; every row
  * of bucket b has the host-computed id groupA * F + subF == b (bit fields of
- * dj_mix64 as documented at groupA_of / subF_of in dj_kernels.hip); the sorted
+ * dj_mix64 as documented at groupA_of / subF_of in dj_kernels.hip and restated
+ * in bucket_model.hpp); the sorted
  * (key, payload) multiset equals the input's.
  *
  * Keys are distinct multiplicative-hash values with one run of 300 equal
@@ -22,10 +23,10 @@
  *   fullest pass-A group against its capacity for every case.
  * Build/run: tests/test_gpu_bucket_partition.py.
  */
-#include "dj_kernels.hpp"
-#include "dj_rng.h"
+#include "bucket_model.hpp"
+#include "check.hpp"
 
-#include <hip/hip_runtime.h>
+#include "dj_kernels.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -33,15 +34,6 @@
 #include <cstring>
 #include <utility>
 #include <vector>
-
-#define CHECK(c)                                                      \
-  do {                                                                \
-    hipError_t e = (c);                                               \
-    if (e != hipSuccess) {                                            \
-      printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); \
-      exit(1);                                                        \
-    }                                                                 \
-  } while (0)
 
 struct Case {
   int B;
@@ -61,19 +53,6 @@ static const Case kCases[] = {
 
 constexpr int64_t kRunStart = 1000, kRunLen = 300;
 
-static uint32_t bucket_of(int64_t key, int PA, int F)
-{
-  const uint64_t m = dj_mix64((uint64_t)key);
-  const uint32_t g = (uint32_t)(m >> 40) & (uint32_t)(PA - 1);
-  uint32_t sub;
-  if (F <= 256) {
-    sub = (uint32_t)(m >> 32) & (uint32_t)(F - 1);
-  } else {
-    sub = ((uint32_t)(m >> 32) & 255u) | (((uint32_t)(m >> 50) & (uint32_t)((F >> 8) - 1)) << 8);
-  }
-  return g * (uint32_t)F + sub;
-}
-
 static void make_inputs(const Case& c, std::vector<int64_t>& keys, std::vector<int64_t>& pay)
 {
   keys.resize((size_t)c.n);
@@ -91,7 +70,7 @@ static bool check_inputs(const Case& c, const std::vector<int64_t>& keys)
 {
   const int PA = dj::bucket_groups_for(c.B);
   std::vector<int64_t> cnt((size_t)PA, 0);
-  for (int64_t k : keys) cnt[(dj_mix64((uint64_t)k) >> 40) & (uint64_t)(PA - 1)]++;
+  for (int64_t k : keys) cnt[group_of(k, PA)]++;
   const int64_t fullest = *std::max_element(cnt.begin(), cnt.end());
   const int64_t capA = dj::slack_capA(c.n, PA);
   printf("inputs B=%d n=%lld PA=%d: fullest group %lld of slack_capA %lld\n", c.B,
@@ -124,8 +103,8 @@ static int run_case(const Case& c, bool slack, const std::vector<int64_t>& keys,
   CHECK(hipMalloc(&d_ovf, 4));
   CHECK(hipMemcpy(d_keys, keys.data(), (size_t)n * 8, hipMemcpyHostToDevice));
   CHECK(hipMemcpy(d_pay, pay.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-  CHECK(hipMemset(d_out, 0xEE, (size_t)n * 16));
-  CHECK(hipMemset(d_offsets, 0xEE, (size_t)(B + 1) * 8));
+  CHECK(hipMemset(d_out, kPoison, (size_t)n * 16));
+  CHECK(hipMemset(d_offsets, kPoison, (size_t)(B + 1) * 8));
   CHECK(hipMemset(d_ovf, 0, 4));
 
   dj::bucket_partition2(d_keys, c.null_pay ? nullptr : d_pay, n, B, d_tmp, d_counts, d_totals,

@@ -1,9 +1,9 @@
 /*
  * dtype_loopback.cpp — narrow keys and 1-/2-/4-/8-byte payload columns
- * across G ranks on ONE GPU. Ranks run as host threads, each with a small
+ * across G ranks on ONE GPU. Ranks run as host threads, each with the
  * loopback implementation of the public Communicator interface
- * (include/communicator.hpp) that hands device buffers over through an
- * in-process mailbox.
+ * (loopback.hpp) that hands device buffers over through an in-process
+ * mailbox; upload and read-back are those of host_table.hpp.
  *
  * Global tables, 40 000 x 40 000 rows:
  *   left  = (key INT16, UINT8, FLOAT64, rowid INT64)
@@ -23,108 +23,14 @@
  * usage: dtype_loopback G nvlink_domain_size compression
  * Build/run: tests/test_gpu_dtypes.py::test_dtype_loopback.
  */
-#include "communicator.hpp"
+#include "host_table.hpp"
+#include "loopback.hpp"
+
 #include "compression.hpp"
 #include "distributed_join.hpp"
 #include "shuffle_on.hpp"
 
-#include "../../distributed_join_amd/csrc/dj_rng.h"
-
-#include <hip/hip_runtime.h>
-
-#include <condition_variable>
-#include <cstdio>
-#include <cstdlib>
-#include <map>
-#include <mutex>
-#include <cstring>
-#include <thread>
-#include <tuple>
 #include <vector>
-
-#define CHECK(c)                                                      \
-  do {                                                                \
-    hipError_t e = (c);                                               \
-    if (e != hipSuccess) {                                            \
-      printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); \
-      exit(1);                                                        \
-    }                                                                 \
-  } while (0)
-
-/* ---------------- loopback transport ---------------- */
-
-struct Mailbox {
-  struct Msg {
-    const void* src;
-    size_t bytes;
-    bool consumed;
-  };
-  std::mutex m;
-  std::condition_variable cv;
-  std::map<std::tuple<int, int, long>, Msg> msgs;  // (src, dst, seq of the pair)
-  std::map<std::pair<int, int>, long> send_seq, recv_seq;
-
-  void post(int src, int dst, const void* buf, size_t bytes)
-  {
-    std::lock_guard<std::mutex> g(m);
-    msgs[{src, dst, send_seq[{src, dst}]++}] = Msg{buf, bytes, false};
-    cv.notify_all();
-  }
-  void fetch(int src, int dst, void* out, size_t bytes)
-  {
-    std::unique_lock<std::mutex> g(m);
-    const long seq = recv_seq[{src, dst}]++;
-    cv.wait(g, [&] { return msgs.count({src, dst, seq}) != 0; });
-    Msg& msg = msgs[{src, dst, seq}];
-    if (msg.bytes != bytes) {
-      printf("loopback size mismatch %zu vs %zu\n", msg.bytes, bytes);
-      exit(1);
-    }
-    CHECK(hipMemcpy(out, msg.src, bytes, hipMemcpyDeviceToDevice));
-    msg.consumed = true;
-    cv.notify_all();
-  }
-  void drain(int src)
-  {
-    std::unique_lock<std::mutex> g(m);
-    cv.wait(g, [&] {
-      for (auto& kv : msgs)
-        if (std::get<0>(kv.first) == src && !kv.second.consumed) return false;
-      return true;
-    });
-  }
-};
-
-class LoopbackComm : public Communicator {
- public:
-  LoopbackComm(int rank, int size, Mailbox* mb) : mb_(mb)
-  {
-    mpi_rank = rank;
-    mpi_size = size;
-    current_device = 0;
-  }
-  void initialize() override {}
-  void start() override {}
-  void stop() override
-  {
-    mb_->drain(mpi_rank);
-    CHECK(hipDeviceSynchronize());
-  }
-  void send(const void* buf, int64_t count, int element_size, int dest) override
-  {
-    CHECK(hipDeviceSynchronize());
-    mb_->post(mpi_rank, dest, buf, (size_t)count * element_size);
-  }
-  void recv(void* buf, int64_t count, int element_size, int source) override
-  {
-    mb_->fetch(source, mpi_rank, buf, (size_t)count * element_size);
-  }
-  void finalize() override {}
-  bool group_by_batch() override { return true; }
-
- private:
-  Mailbox* mb_;
-};
 
 /* ---------------- tables ---------------- */
 
@@ -142,14 +48,8 @@ static uint32_t f32_bits_of(int64_t rowid) { return (uint32_t)dj_mix64((uint64_t
 template <typename T>
 static std::unique_ptr<cudf::column> upload(cudf::type_id id, const std::vector<T>& v)
 {
-  auto col = std::make_unique<cudf::column>(cudf::data_type(id), (cudf::size_type)v.size());
-  if (cudf::size_of(col->type()) != (cudf::size_type)sizeof(T)) {
-    printf("size_of mismatch for type %d\n", (int)id);
-    exit(1);
-  }
-  if (!v.empty())
-    CHECK(hipMemcpy(col->head(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return col;
+  if (width_of(id) != (int)sizeof(T)) FAIL("size_of mismatch for type %d", (int)id);
+  return device_fixed(id, v.data(), (int64_t)v.size(), (int)sizeof(T));
 }
 
 /* rows [row0, row0 + rows) of a global table */
@@ -183,14 +83,11 @@ static std::unique_ptr<cudf::table> make_table(int64_t row0, int64_t rows, bool 
 template <typename T>
 static std::vector<T> host_of(const cudf::column& col, cudf::type_id want)
 {
-  if (col.type().id() != want) {
-    printf("JOIN OUTPUT SCHEMA WRONG (type %d, want %d)\n", (int)col.type().id(), (int)want);
-    exit(1);
-  }
-  std::vector<T> v((size_t)col.size());
-  if (col.size())
-    CHECK(hipMemcpy(v.data(), col.head(), (size_t)col.size() * sizeof(T), hipMemcpyDeviceToHost));
-  return v;
+  if (col.type().id() != want)
+    FAIL("JOIN OUTPUT SCHEMA WRONG (type %d, want %d)", (int)col.type().id(), (int)want);
+  /* from_device sign-extends to 64 bits; narrowing to T gives the bits back */
+  const HCol c = from_device(col);
+  return std::vector<T>(c.v.begin(), c.v.end());
 }
 
 /* verifies every row, then folds (key, lrowid, rrowid) into an
@@ -264,22 +161,16 @@ int main(int argc, char** argv)
     Mailbox mb;
     std::vector<uint64_t> sums((size_t)G, 0);
     std::vector<int64_t> rows((size_t)G, 0);
-    std::vector<std::thread> th;
-    for (int r = 0; r < G; r++) {
-      th.emplace_back([&, r] {
-        CHECK(hipSetDevice(0));
-        LoopbackComm comm(r, G, &mb);
-        const int64_t row0 = kRows * r / G, row1 = kRows * (r + 1) / G;
-        auto left = make_table(row0, row1 - row0, true);
-        auto right = make_table(row0, row1 - row0, false);
-        auto lo = generate_compression_options_distributed(left->view(), compress);
-        auto ro = generate_compression_options_distributed(right->view(), compress);
-        auto res = distributed_inner_join(left->view(), right->view(), {0}, {0}, &comm, lo, ro,
-                                          2, false, nullptr, nvl);
-        checksum(*res, &sums[(size_t)r], &rows[(size_t)r]);
-      });
-    }
-    for (auto& t : th) t.join();
+    run_ranks(G, &mb, [&](int r, Communicator* comm) {
+      const int64_t row0 = kRows * r / G, row1 = kRows * (r + 1) / G;
+      auto left = make_table(row0, row1 - row0, true);
+      auto right = make_table(row0, row1 - row0, false);
+      auto lo = generate_compression_options_distributed(left->view(), compress);
+      auto ro = generate_compression_options_distributed(right->view(), compress);
+      auto res = distributed_inner_join(left->view(), right->view(), {0}, {0}, comm, lo, ro,
+                                        2, false, nullptr, nvl);
+      checksum(*res, &sums[(size_t)r], &rows[(size_t)r]);
+    });
     uint64_t got_sum = 0;
     int64_t got_rows = 0;
     for (int r = 0; r < G; r++) {

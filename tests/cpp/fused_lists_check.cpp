@@ -6,7 +6,8 @@
  *
  * Host reference: slice of a key = (dj_murmur3_int64(key, seed) % nparts_rank)
  * * PA + groupA, bucket = groupA * F + subF, with groupA and subF the dj_mix64
- * bit fields documented at groupA_of / subF_of in dj_kernels.hip. Payloads
+ * bit fields documented at groupA_of / subF_of in dj_kernels.hip and restated
+ * in bucket_model.hpp. Payloads
  * name the input row (7*i+3, or the row index under a null payload pointer),
  * so "the multiset of a slice equals the input's" is checked as: every stored
  * row equals its input row, sits in the slice its key asks for, and no input
@@ -40,11 +41,10 @@
  *   DJ_CHECK_ERROR must end the process with status 1 before any launch.
  * Build/run: tests/test_gpu_fused_lists.py.
  */
-#include "dj_hash.h"
-#include "dj_kernels.hpp"
-#include "dj_rng.h"
+#include "bucket_model.hpp"
+#include "check.hpp"
 
-#include <hip/hip_runtime.h>
+#include "dj_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -56,51 +56,12 @@
 #include <string>
 #include <vector>
 
-#define CHECK(c)                                                      \
-  do {                                                                \
-    hipError_t e = (c);                                               \
-    if (e != hipSuccess) {                                            \
-      printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); \
-      exit(1);                                                        \
-    }                                                                 \
-  } while (0)
-
 static dj::BucketPartitionShape g_sh;
-
-constexpr int kGuard = 64, kGuardWords = 16;
-constexpr int kPoison = 0xEE;
 
 static double g_slowest_ms = 0;
 static size_t g_largest_bytes = 0;
 
 /* ---------------- host reference ---------------- */
-
-static uint32_t group_of(int64_t key, int PA)
-{
-  return (uint32_t)(dj_mix64((uint64_t)key) >> 40) & (uint32_t)(PA - 1);
-}
-static uint32_t sub_of(int64_t key, int F)
-{
-  const uint64_t m = dj_mix64((uint64_t)key);
-  if (F <= 256) return (uint32_t)(m >> 32) & (uint32_t)(F - 1);
-  return ((uint32_t)(m >> 32) & 255u) | (((uint32_t)(m >> 50) & (uint32_t)((F >> 8) - 1)) << 8);
-}
-static uint32_t slice_of_key(int64_t key, int npr, uint32_t seed, int PA)
-{
-  return (dj_murmur3_int64(key, seed) % (uint32_t)npr) * (uint32_t)PA + group_of(key, PA);
-}
-/* distinct keys: an odd multiplier is a bijection of the index */
-static int64_t hkey(uint64_t stream, uint64_t i)
-{
-  return (int64_t)(((stream << 40) + i + 1) * 0x9E3779B97F4A7C15ULL);
-}
-static bool all_poison(const void* p, size_t bytes)
-{
-  const unsigned char* b = (const unsigned char*)p;
-  for (size_t i = 0; i < bytes; i++)
-    if (b[i] != kPoison) return false;
-  return true;
-}
 
 struct Fails {
   int bad = 0;
@@ -162,22 +123,22 @@ static int run_fused(const FusedCase& c, const std::vector<int64_t>& keys,
   CHECK(hipMalloc(&d_counts, (size_t)g_sh.bucket_blocks * P * 4));
   CHECK(hipMalloc(&d_totals, (size_t)P * 4));
   CHECK(hipMalloc(&d_off, (size_t)(P + 1 + kGuardWords) * 8));
-  CHECK(hipMalloc(&d_ok, (n + kGuard) * 8));
-  CHECK(hipMalloc(&d_op, (n + kGuard) * 8));
+  CHECK(hipMalloc(&d_ok, (n + kGuardRows) * 8));
+  CHECK(hipMalloc(&d_op, (n + kGuardRows) * 8));
   const size_t bytes = 2 * n * 8 + (size_t)(g_sh.bucket_blocks + 1) * P * 4 +
-                       (size_t)(P + 1 + kGuardWords) * 8 + 2 * (n + kGuard) * 8;
+                       (size_t)(P + 1 + kGuardWords) * 8 + 2 * (n + kGuardRows) * 8;
   g_largest_bytes = std::max(g_largest_bytes, bytes);
   CHECK(hipMemcpy(d_keys, keys.data(), n * 8, hipMemcpyHostToDevice));
   CHECK(hipMemcpy(d_pay, pay.data(), n * 8, hipMemcpyHostToDevice));
   CHECK(hipMemset(d_off, kPoison, (size_t)(P + 1 + kGuardWords) * 8));
-  CHECK(hipMemset(d_ok, kPoison, (n + kGuard) * 8));
-  CHECK(hipMemset(d_op, kPoison, (n + kGuard) * 8));
+  CHECK(hipMemset(d_ok, kPoison, (n + kGuardRows) * 8));
+  CHECK(hipMemset(d_op, kPoison, (n + kGuardRows) * 8));
 
   dj::fused_partition(d_keys, c.null_pay ? nullptr : d_pay, c.n, c.npr, c.seed, c.PA, d_counts,
                       d_totals, d_off, d_ok, d_op, nullptr);
   CHECK(hipDeviceSynchronize());
 
-  std::vector<int64_t> off((size_t)P + 1 + kGuardWords), ok(n + kGuard), op(n + kGuard);
+  std::vector<int64_t> off((size_t)P + 1 + kGuardWords), ok(n + kGuardRows), op(n + kGuardRows);
   CHECK(hipMemcpy(off.data(), d_off, off.size() * 8, hipMemcpyDeviceToHost));
   CHECK(hipMemcpy(ok.data(), d_ok, ok.size() * 8, hipMemcpyDeviceToHost));
   CHECK(hipMemcpy(op.data(), d_op, op.size() * 8, hipMemcpyDeviceToHost));
@@ -188,8 +149,9 @@ static int run_fused(const FusedCase& c, const std::vector<int64_t>& keys,
   Fails fail;
   if (!all_poison(off.data() + P + 1, kGuardWords * 8))
     fail("guard after offsets[P] written", 0, 0);
-  if (!all_poison(ok.data() + n, kGuard * 8)) fail("guard after the key column written", 0, 0);
-  if (!all_poison(op.data() + n, kGuard * 8)) fail("guard after the payload column written", 0, 0);
+  if (!all_poison(ok.data() + n, kGuardRows * 8)) fail("guard after the key column written", 0, 0);
+  if (!all_poison(op.data() + n, kGuardRows * 8))
+    fail("guard after the payload column written", 0, 0);
   if (off[0] != 0) fail("offsets[0] != 0", off[0], 0);
   if (off[(size_t)P] != c.n) fail("offsets[P] != n", off[(size_t)P], c.n);
   bool monotone = off[0] == 0 && off[(size_t)P] == c.n;
@@ -360,23 +322,23 @@ static int run_lists(const Layout& L)
   CHECK(hipMalloc(&d_pay, nin * 8));
   CHECK(hipMalloc(&d_seg, L.seg.size() * 8));
   CHECK(hipMalloc(&d_gb, L.gbase.size() * 8));
-  CHECK(hipMalloc(&d_out, (total + kGuard) * 16));
+  CHECK(hipMalloc(&d_out, (total + kGuardRows) * 16));
   CHECK(hipMalloc(&d_off, (size_t)(B + 1 + kGuardWords) * 8));
-  const size_t bytes = 2 * nin * 8 + (L.seg.size() + L.gbase.size()) * 8 + (total + kGuard) * 16 +
-                       (size_t)(B + 1 + kGuardWords) * 8;
+  const size_t bytes = 2 * nin * 8 + (L.seg.size() + L.gbase.size()) * 8 +
+                       (total + kGuardRows) * 16 + (size_t)(B + 1 + kGuardWords) * 8;
   g_largest_bytes = std::max(g_largest_bytes, bytes);
   CHECK(hipMemcpy(d_keys, L.keys.data(), L.keys.size() * 8, hipMemcpyHostToDevice));
   CHECK(hipMemcpy(d_pay, L.pay.data(), L.pay.size() * 8, hipMemcpyHostToDevice));
   CHECK(hipMemcpy(d_seg, L.seg.data(), L.seg.size() * 8, hipMemcpyHostToDevice));
   CHECK(hipMemcpy(d_gb, L.gbase.data(), L.gbase.size() * 8, hipMemcpyHostToDevice));
-  CHECK(hipMemset(d_out, kPoison, (total + kGuard) * 16));
+  CHECK(hipMemset(d_out, kPoison, (total + kGuardRows) * 16));
   CHECK(hipMemset(d_off, kPoison, (size_t)(B + 1 + kGuardWords) * 8));
 
   dj::subpart_lists(d_keys, L.null_pay ? nullptr : d_pay, d_seg, L.G, L.PA, L.F, d_gb, d_out,
                     d_off, nullptr);
   CHECK(hipDeviceSynchronize());
 
-  std::vector<longlong2> out(total + kGuard);
+  std::vector<longlong2> out(total + kGuardRows);
   std::vector<int64_t> off((size_t)B + 1 + kGuardWords);
   CHECK(hipMemcpy(out.data(), d_out, out.size() * 16, hipMemcpyDeviceToHost));
   CHECK(hipMemcpy(off.data(), d_off, off.size() * 8, hipMemcpyDeviceToHost));
@@ -391,7 +353,7 @@ static int run_lists(const Layout& L)
   std::sort(by_pay.begin(), by_pay.end());
 
   Fails fail;
-  if (!all_poison(out.data() + total, kGuard * 16))
+  if (!all_poison(out.data() + total, kGuardRows * 16))
     fail("guard rows after out_pairs written", 0, 0);
   if (!all_poison(off.data() + B + 1, kGuardWords * 8))
     fail("guard after bucket_offsets[PA*F] written", 0, 0);

@@ -51,10 +51,10 @@
  *   must end the process with status 1 before any launch.
  * Build/run: tests/test_gpu_lds_join.py.
  */
-#include "dj_kernels.hpp"
-#include "dj_rng.h"
+#include "bucket_model.hpp" /* kGuardRows, kPoison */
+#include "check.hpp"
 
-#include <hip/hip_runtime.h>
+#include "dj_kernels.hpp"
 
 #include <algorithm>
 #include <array>
@@ -66,15 +66,6 @@
 #include <string>
 #include <unordered_map>
 #include <vector>
-
-#define CHECK(c)                                                      \
-  do {                                                                \
-    hipError_t e = (c);                                               \
-    if (e != hipSuccess) {                                            \
-      printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); \
-      exit(1);                                                        \
-    }                                                                 \
-  } while (0)
 
 struct Row {
   int64_t k, v;
@@ -99,7 +90,6 @@ struct Case {
 };
 
 static dj::LdsJoinShape g_shape;
-constexpr int64_t kGuardRows = 64;
 constexpr int64_t kFill = (int64_t)0xEEEEEEEEEEEEEEEEULL;
 
 [[noreturn]] static void bad_inputs(const char* fmt, ...)
@@ -781,7 +771,7 @@ static void run_case(const Case& c, const Ref& ref, bool slack)
   o.nflags = Bk;
   for (int i = 0; i < 4; i++) {
     o.col[i] = dev.alloc<int64_t>((size_t)(o.cap + kGuardRows));
-    CHECK(hipMemset(o.col[i], 0xEE, (size_t)(o.cap + kGuardRows) * 8));
+    CHECK(hipMemset(o.col[i], kPoison, (size_t)(o.cap + kGuardRows) * 8));
   }
   o.counter = dev.alloc<int64_t>(1);
   o.flags = dev.alloc<uint32_t>((size_t)Bk);

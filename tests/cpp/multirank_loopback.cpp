@@ -1,7 +1,7 @@
 /*
  * multirank_loopback.cpp — multi-rank exercise of the C++ drop-in
  * orchestration on ONE GPU: G ranks run as host threads, each with its own
- * `LoopbackCommunicator` (a user-style implementation of the public
+ * `LoopbackComm` (loopback.hpp: a user-style implementation of the public
  * Communicator interface — include/communicator.hpp — exchanging device
  * buffers through an in-process mailbox with D2D copies).
  *
@@ -14,8 +14,9 @@
  *
  * Build/run: see tests/test_gpu_cpp_api.py::test_multirank_loopback.
  */
+#include "loopback.hpp"
+
 #include "all_to_all_comm.hpp"
-#include "communicator.hpp"
 #include "compression.hpp"
 #include "distribute_table.hpp"
 #include "distributed_join.hpp"
@@ -23,105 +24,9 @@
 
 #include "../../distributed_join_amd/csrc/dj_rng.h"
 
-#include <hip/hip_runtime.h>
-
-#include <condition_variable>
-#include <cstdio>
 #include <cstring>
 #include <map>
-#include <mutex>
-#include <thread>
 #include <vector>
-
-#define CHECK(c)                                                      \
-  do {                                                                \
-    hipError_t e = (c);                                               \
-    if (e != hipSuccess) {                                            \
-      printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); \
-      exit(1);                                                        \
-    }                                                                 \
-  } while (0)
-
-/* ---------------- in-process mailbox transport ---------------- */
-
-struct Mailbox {
-  struct Msg {
-    const void* src;
-    size_t bytes;
-    bool consumed{false};
-  };
-  std::mutex m;
-  std::condition_variable cv;
-  /* key: (src_rank, dst_rank, seq of that pair) */
-  std::map<std::tuple<int, int, long>, Msg> msgs;
-  std::map<std::pair<int, int>, long> send_seq, recv_seq;
-
-  void post(int src, int dst, const void* buf, size_t bytes)
-  {
-    std::lock_guard<std::mutex> g(m);
-    long seq = send_seq[{src, dst}]++;
-    msgs[{src, dst, seq}] = Msg{buf, bytes, false};
-    cv.notify_all();
-  }
-  /* blocks until the matching send arrives, then D2D-copies it */
-  void fetch(int src, int dst, void* out, size_t bytes)
-  {
-    std::unique_lock<std::mutex> g(m);
-    long seq = recv_seq[{src, dst}]++;
-    cv.wait(g, [&] { return msgs.count({src, dst, seq}) != 0; });
-    Msg& msg = msgs[{src, dst, seq}];
-    if (msg.bytes != bytes) {
-      printf("loopback size mismatch %zu vs %zu\n", msg.bytes, bytes);
-      exit(1);
-    }
-    CHECK(hipMemcpy(out, msg.src, bytes, hipMemcpyDeviceToDevice));
-    msg.consumed = true;
-    cv.notify_all();
-  }
-  void wait_all_consumed(int src)
-  {
-    std::unique_lock<std::mutex> g(m);
-    cv.wait(g, [&] {
-      for (auto& kv : msgs)
-        if (std::get<0>(kv.first) == src && !kv.second.consumed) return false;
-      return true;
-    });
-  }
-};
-
-/* user-style Communicator implementation against the public header */
-class LoopbackCommunicator : public Communicator {
- public:
-  LoopbackCommunicator(int rank, int size, Mailbox* mb) : mb_(mb)
-  {
-    mpi_rank = rank;
-    mpi_size = size;
-    current_device = 0;
-  }
-  void initialize() override {}
-  void start() override {}
-  void stop() override
-  {
-    /* block until every posted send was consumed and device work drained —
-     * the blocking contract of Communicator::stop */
-    mb_->wait_all_consumed(mpi_rank);
-    CHECK(hipDeviceSynchronize());
-  }
-  void send(const void* buf, int64_t count, int element_size, int dest) override
-  {
-    CHECK(hipDeviceSynchronize());  // payload must be ready before posting
-    mb_->post(mpi_rank, dest, buf, (size_t)count * element_size);
-  }
-  void recv(void* buf, int64_t count, int element_size, int source) override
-  {
-    mb_->fetch(source, mpi_rank, buf, (size_t)count * element_size);
-  }
-  void finalize() override {}
-  bool group_by_batch() override { return true; }
-
- private:
-  Mailbox* mb_;
-};
 
 /* ---------------- helpers ---------------- */
 
@@ -286,7 +191,7 @@ int main(int argc, char** argv)
     auto left = make_rank_tables(n_global, n_global, 0, true, key_mode);
     auto right = make_rank_tables(n_global, n_global, 0, false, key_mode);
     Mailbox mb;
-    LoopbackCommunicator comm(0, 1, &mb);
+    LoopbackComm comm(0, 1, &mb);
     auto opts = generate_compression_options_distributed(left->view(), false);
     auto res = distributed_inner_join(left->view(), right->view(), {0}, {0}, &comm, opts,
                                       opts, 1, false, nullptr, 1);
@@ -297,39 +202,33 @@ int main(int argc, char** argv)
   Mailbox mb;
   std::vector<uint64_t> sums(G);
   std::vector<int64_t> rows(G);
-  std::vector<std::thread> threads;
-  for (int r = 0; r < G; r++) {
-    threads.emplace_back([&, r] {
-      CHECK(hipSetDevice(0));
-      int64_t per = n_global / G;
-      auto left = make_rank_tables(n_global, per, r * per, true, key_mode);
-      auto right = make_rank_tables(n_global, per, r * per, false, key_mode);
-      LoopbackCommunicator comm(r, G, &mb);
-      /* alternate per-rank-invariant variants across runs of this binary via
-       * argv: nvlink_domain_size and compression are exercised by the python
-       * wrapper invoking multiple configurations */
-      const int nvl = (argc > 4) ? atoi(argv[4]) : 1;
-      const bool compress = (argc > 5) && atoi(argv[5]) != 0;
-      /* sampling selector on rank 0 + broadcast over the loopback transport
-       * (reference compression.cpp:36-130 flow); every rank must end up
-       * with rank 0's choice */
-      auto sel = (r == 0) ? generate_auto_select_compression_options(left->view())
-                          : std::vector<ColumnCompressionOptions>{};
-      auto bopts = broadcast_compression_options(left->view(), sel, &comm);
-      if (bopts.size() != 2 ||
-          bopts[0].compression_method != CompressionMethod::cascaded ||
-          bopts[0].cascaded_format.use_bp != 1) {
-        printf("BCAST OPTS WRONG rank %d\n", r);
-        exit(1);
-      }
-      auto opts = compress ? bopts
-                           : generate_compression_options_distributed(left->view(), compress);
-      auto res = distributed_inner_join(left->view(), right->view(), {0}, {0}, &comm, opts,
-                                        opts, over_decom, false, nullptr, nvl);
-      checksum(*res, &sums[r], &rows[r]);
-    });
-  }
-  for (auto& t : threads) t.join();
+  run_ranks(G, &mb, [&](int r, Communicator* comm) {
+    int64_t per = n_global / G;
+    auto left = make_rank_tables(n_global, per, r * per, true, key_mode);
+    auto right = make_rank_tables(n_global, per, r * per, false, key_mode);
+    /* alternate per-rank-invariant variants across runs of this binary via
+     * argv: nvlink_domain_size and compression are exercised by the python
+     * wrapper invoking multiple configurations */
+    const int nvl = (argc > 4) ? atoi(argv[4]) : 1;
+    const bool compress = (argc > 5) && atoi(argv[5]) != 0;
+    /* sampling selector on rank 0 + broadcast over the loopback transport
+     * (reference compression.cpp:36-130 flow); every rank must end up
+     * with rank 0's choice */
+    auto sel = (r == 0) ? generate_auto_select_compression_options(left->view())
+                        : std::vector<ColumnCompressionOptions>{};
+    auto bopts = broadcast_compression_options(left->view(), sel, comm);
+    if (bopts.size() != 2 ||
+        bopts[0].compression_method != CompressionMethod::cascaded ||
+        bopts[0].cascaded_format.use_bp != 1) {
+      printf("BCAST OPTS WRONG rank %d\n", r);
+      exit(1);
+    }
+    auto opts = compress ? bopts
+                         : generate_compression_options_distributed(left->view(), compress);
+    auto res = distributed_inner_join(left->view(), right->view(), {0}, {0}, comm, opts,
+                                      opts, over_decom, false, nullptr, nvl);
+    checksum(*res, &sums[r], &rows[r]);
+  });
 
   uint64_t got_sum = 0;
   int64_t got_rows = 0;
@@ -344,48 +243,42 @@ int main(int argc, char** argv)
   {
     Mailbox mb2;
     std::vector<int> shuffle_ok(G, 0), roundtrip_ok(G, 0);
-    std::vector<std::thread> th2;
     const int64_t n = 100000;
-    for (int r = 0; r < G; r++) {
-      th2.emplace_back([&, r] {
-        CHECK(hipSetDevice(0));
-        LoopbackCommunicator comm(r, G, &mb2);
-        /* per-rank input: arbitrary int64 keys */
-        auto t = make_rank_tables(n, n / G, r * (n / G), false);
-        auto opts = generate_compression_options_distributed(t->view(), false);
-        auto shuffled = shuffle_on(t->view(), {0}, &comm, opts,
-                                   cudf::hash_id::HASH_IDENTITY, 0);
-        int64_t m = shuffled->num_rows();
-        std::vector<int64_t> keys(m);
-        CHECK(hipMemcpy(keys.data(), shuffled->get_column(0).head(), m * 8,
-                        hipMemcpyDeviceToHost));
-        bool ok = true;
-        for (int64_t i = 0; i < m; i++)
-          ok &= ((uint32_t)((uint64_t)keys[i] & 0xFFFFFFFFu) % (uint32_t)G == (uint32_t)r);
-        shuffle_ok[r] = ok ? 1 : 0;
+    run_ranks(G, &mb2, [&](int r, Communicator* comm) {
+      /* per-rank input: arbitrary int64 keys */
+      auto t = make_rank_tables(n, n / G, r * (n / G), false);
+      auto opts = generate_compression_options_distributed(t->view(), false);
+      auto shuffled = shuffle_on(t->view(), {0}, comm, opts,
+                                 cudf::hash_id::HASH_IDENTITY, 0);
+      int64_t m = shuffled->num_rows();
+      std::vector<int64_t> keys(m);
+      CHECK(hipMemcpy(keys.data(), shuffled->get_column(0).head(), m * 8,
+                      hipMemcpyDeviceToHost));
+      bool ok = true;
+      for (int64_t i = 0; i < m; i++)
+        ok &= ((uint32_t)((uint64_t)keys[i] & 0xFFFFFFFFu) % (uint32_t)G == (uint32_t)r);
+      shuffle_ok[r] = ok ? 1 : 0;
 
-        /* distribute/collect round trip (global table significant on root) */
-        std::unique_ptr<cudf::table> global;
-        cudf::table_view gview;
-        if (r == 0) {
-          global = make_rank_tables(n, n, 0, true);
-          gview = global->view();
-        }
-        auto local = distribute_table(gview, &comm);
-        auto merged = collect_tables(local->view(), &comm);
-        if (r == 0) {
-          std::vector<int64_t> a(n), b(n);
-          CHECK(hipMemcpy(a.data(), global->get_column(0).head(), n * 8,
-                          hipMemcpyDeviceToHost));
-          CHECK(hipMemcpy(b.data(), merged->get_column(0).head(), n * 8,
-                          hipMemcpyDeviceToHost));
-          roundtrip_ok[0] = (merged->num_rows() == n && a == b) ? 1 : 0;
-        } else {
-          roundtrip_ok[r] = (merged == nullptr) ? 1 : 0;
-        }
-      });
-    }
-    for (auto& t : th2) t.join();
+      /* distribute/collect round trip (global table significant on root) */
+      std::unique_ptr<cudf::table> global;
+      cudf::table_view gview;
+      if (r == 0) {
+        global = make_rank_tables(n, n, 0, true);
+        gview = global->view();
+      }
+      auto local = distribute_table(gview, comm);
+      auto merged = collect_tables(local->view(), comm);
+      if (r == 0) {
+        std::vector<int64_t> a(n), b(n);
+        CHECK(hipMemcpy(a.data(), global->get_column(0).head(), n * 8,
+                        hipMemcpyDeviceToHost));
+        CHECK(hipMemcpy(b.data(), merged->get_column(0).head(), n * 8,
+                        hipMemcpyDeviceToHost));
+        roundtrip_ok[0] = (merged->num_rows() == n && a == b) ? 1 : 0;
+      } else {
+        roundtrip_ok[r] = (merged == nullptr) ? 1 : 0;
+      }
+    });
     for (int r = 0; r < G; r++) {
       if (!shuffle_ok[r]) {
         printf("SHUFFLE PLACEMENT MISMATCH rank %d\n", r);
@@ -409,7 +302,7 @@ int main(int argc, char** argv)
     int64_t want_r;
     {
       Mailbox mb1;
-      LoopbackCommunicator c1(0, 1, &mb1);
+      LoopbackComm c1(0, 1, &mb1);
       auto l = make_rank_strtable(ns, ns, 0, true);
       auto r = make_rank_strtable(ns, ns, 0, false);
       auto o = generate_compression_options_distributed(l.view(), compress);
@@ -420,21 +313,15 @@ int main(int argc, char** argv)
     Mailbox mb2;
     std::vector<uint64_t> ssums(G);
     std::vector<int64_t> srows(G);
-    std::vector<std::thread> th;
-    for (int r = 0; r < G; r++) {
-      th.emplace_back([&, r] {
-        CHECK(hipSetDevice(0));
-        int64_t per = ns / G;
-        auto l = make_rank_strtable(ns, per, r * per, true);
-        auto rt = make_rank_strtable(ns, per, r * per, false);
-        LoopbackCommunicator comm(r, G, &mb2);
-        auto o = generate_compression_options_distributed(l.view(), compress);
-        auto res = distributed_inner_join(l.view(), rt.view(), {0}, {0}, &comm, o, o,
-                                          over_decom, false, nullptr, nvl);
-        checksum_str(*res, &ssums[r], &srows[r]);
-      });
-    }
-    for (auto& t : th) t.join();
+    run_ranks(G, &mb2, [&](int r, Communicator* comm) {
+      int64_t per = ns / G;
+      auto l = make_rank_strtable(ns, per, r * per, true);
+      auto rt = make_rank_strtable(ns, per, r * per, false);
+      auto o = generate_compression_options_distributed(l.view(), compress);
+      auto res = distributed_inner_join(l.view(), rt.view(), {0}, {0}, comm, o, o,
+                                        over_decom, false, nullptr, nvl);
+      checksum_str(*res, &ssums[r], &srows[r]);
+    });
     uint64_t gs = 0;
     int64_t gr = 0;
     for (int r = 0; r < G; r++) {
@@ -489,7 +376,7 @@ int main(int argc, char** argv)
     int64_t want_r;
     {
       Mailbox mb1;
-      LoopbackCommunicator c1(0, 1, &mb1);
+      LoopbackComm c1(0, 1, &mb1);
       auto l = make_mk(nm, 0);
       auto r = make_mk(nm, 1000000);
       auto o = generate_compression_options_distributed(l->view(), false);
@@ -500,21 +387,15 @@ int main(int argc, char** argv)
     Mailbox mb3;
     std::vector<uint64_t> msums(G);
     std::vector<int64_t> mrows(G);
-    std::vector<std::thread> th;
-    for (int r = 0; r < G; r++) {
-      th.emplace_back([&, r] {
-        CHECK(hipSetDevice(0));
-        int64_t per = nm / G;
-        auto l = make_mk(per, (int64_t)r * per);
-        auto rt = make_mk(per, 1000000 + (int64_t)r * per);
-        LoopbackCommunicator comm(r, G, &mb3);
-        auto o = generate_compression_options_distributed(l->view(), false);
-        auto res = distributed_inner_join(l->view(), rt->view(), {0, 1}, {0, 1}, &comm, o, o,
-                                          1, false, nullptr, G);
-        checksum6(*res, &msums[r], &mrows[r]);
-      });
-    }
-    for (auto& t : th) t.join();
+    run_ranks(G, &mb3, [&](int r, Communicator* comm) {
+      int64_t per = nm / G;
+      auto l = make_mk(per, (int64_t)r * per);
+      auto rt = make_mk(per, 1000000 + (int64_t)r * per);
+      auto o = generate_compression_options_distributed(l->view(), false);
+      auto res = distributed_inner_join(l->view(), rt->view(), {0, 1}, {0, 1}, comm, o, o,
+                                        1, false, nullptr, G);
+      checksum6(*res, &msums[r], &mrows[r]);
+    });
     uint64_t gs = 0;
     int64_t gr = 0;
     for (int r = 0; r < G; r++) {

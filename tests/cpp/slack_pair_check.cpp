@@ -4,9 +4,9 @@
  * bucket_subpart_slack2_pair_kernel) called directly on two tables at once and
  * compared, exactly, with a host prediction.
  *
- * Host reference: bucket_of(key) = groupA * F + subF from the dj_mix64 bit
- * fields documented at groupA_of / subF_of in dj_kernels.hip (group from
- * >> 40, sub-bucket from >> 32, plus >> 50 when F > 256); per-group and
+ * Host reference (bucket_model.hpp): bucket_of(key) = groupA * F + subF from
+ * the dj_mix64 bit fields documented at groupA_of / subF_of in dj_kernels.hip
+ * (group from >> 40, sub-bucket from >> 32, plus >> 50 when F > 256); per-group and
  * per-bucket counts follow from it. Payloads are 7*i+3 (or the row index i
  * when the payload pointer is null), so a stored row names the input row it
  * must be a copy of: "the multiset of stored rows equals the input's" is
@@ -38,10 +38,10 @@
  *   it was built for or a named situation is absent (needs no GPU).
  * Build/run: tests/test_gpu_slack_pair.py.
  */
-#include "dj_kernels.hpp"
-#include "dj_rng.h"
+#include "bucket_model.hpp"
+#include "check.hpp"
 
-#include <hip/hip_runtime.h>
+#include "dj_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -54,19 +54,8 @@
 #include <string>
 #include <vector>
 
-#define CHECK(c)                                                      \
-  do {                                                                \
-    hipError_t e = (c);                                               \
-    if (e != hipSuccess) {                                            \
-      printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); \
-      exit(1);                                                        \
-    }                                                                 \
-  } while (0)
-
 static dj::BucketPartitionShape g_sh;
 
-constexpr int kGuardRows = 64, kGuardWords = 16;
-constexpr int kPoison = 0xEE;
 constexpr int64_t kCapSlack = 0;     /* capB = slack_capB(n, B), the product's */
 constexpr int64_t kCapFullest = -1;  /* capB = host fullest bucket, rounded up to 8 */
 
@@ -86,22 +75,6 @@ struct Case {
 
 /* ---------------- host reference ---------------- */
 
-static uint32_t group_of(int64_t key, int PA)
-{
-  return (uint32_t)(dj_mix64((uint64_t)key) >> 40) & (uint32_t)(PA - 1);
-}
-static uint32_t bucket_of(int64_t key, int PA, int F)
-{
-  const uint64_t m = dj_mix64((uint64_t)key);
-  const uint32_t g = (uint32_t)(m >> 40) & (uint32_t)(PA - 1);
-  uint32_t sub;
-  if (F <= 256) {
-    sub = (uint32_t)(m >> 32) & (uint32_t)(F - 1);
-  } else {
-    sub = ((uint32_t)(m >> 32) & 255u) | (((uint32_t)(m >> 50) & (uint32_t)((F >> 8) - 1)) << 8);
-  }
-  return g * (uint32_t)F + sub;
-}
 static int64_t pay_of(const Table& t, int64_t i) { return t.null_pay ? i : 7 * i + 3; }
 
 struct Pred {
@@ -164,11 +137,7 @@ static Split split_of(int64_t n0, int64_t n1)
 
 /* ---------------- inputs ---------------- */
 
-/* distinct keys: an odd multiplier is a bijection of the index */
-static int64_t hkey(uint64_t stream, uint64_t i)
-{
-  return (int64_t)(((stream << 40) + i + 1) * 0x9E3779B97F4A7C15ULL);
-}
+/* distinct keys: hkey() of bucket_model.hpp */
 static Table distinct(int64_t n, uint64_t stream, int64_t capB = kCapSlack)
 {
   Table t;
@@ -448,14 +417,6 @@ struct DevTable {
   uint32_t *cur = nullptr, *lens = nullptr;
   size_t tmp_rows, out_rows;
 };
-
-static bool all_poison(const void* p, size_t bytes)
-{
-  const unsigned char* b = (const unsigned char*)p;
-  for (size_t i = 0; i < bytes; i++)
-    if (b[i] != kPoison) return false;
-  return true;
-}
 
 static int run_case(const Case& c, const Pred p[2], double* slowest_ms, size_t* largest_bytes)
 {

@@ -1,8 +1,9 @@
 /*
  * stringkey_loopback.cpp — STRING join/shuffle keys across G ranks on ONE
- * GPU. Ranks run as host threads, each with a small loopback implementation
- * of the public Communicator interface (include/communicator.hpp) that
- * hands device buffers over through an in-process mailbox.
+ * GPU. Ranks run as host threads, each with the loopback implementation of
+ * the public Communicator interface (loopback.hpp) that hands device buffers
+ * over through an in-process mailbox; upload and read-back are those of
+ * host_table.hpp.
  *
  * Global tables: 40 000 x 40 000 rows of (key STRING, payload INT64); the
  * key is a formula of the row (length 0-20, duplicates on both sides).
@@ -17,108 +18,16 @@
  * usage: stringkey_loopback G nvlink_domain_size compression
  * Build/run: tests/test_gpu_string_keys.py::test_stringkey_loopback.
  */
-#include "communicator.hpp"
+#include "host_table.hpp"
+#include "loopback.hpp"
+
 #include "compression.hpp"
 #include "distributed_join.hpp"
 #include "shuffle_on.hpp"
 
-#include "../../distributed_join_amd/csrc/dj_rng.h"
-
-#include <hip/hip_runtime.h>
-
-#include <condition_variable>
-#include <cstdio>
-#include <cstdlib>
 #include <map>
-#include <mutex>
 #include <string>
-#include <thread>
-#include <tuple>
 #include <vector>
-
-#define CHECK(c)                                                      \
-  do {                                                                \
-    hipError_t e = (c);                                               \
-    if (e != hipSuccess) {                                            \
-      printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); \
-      exit(1);                                                        \
-    }                                                                 \
-  } while (0)
-
-/* ---------------- loopback transport ---------------- */
-
-struct Mailbox {
-  struct Msg {
-    const void* src;
-    size_t bytes;
-    bool consumed;
-  };
-  std::mutex m;
-  std::condition_variable cv;
-  std::map<std::tuple<int, int, long>, Msg> msgs;  // (src, dst, seq of the pair)
-  std::map<std::pair<int, int>, long> send_seq, recv_seq;
-
-  void post(int src, int dst, const void* buf, size_t bytes)
-  {
-    std::lock_guard<std::mutex> g(m);
-    msgs[{src, dst, send_seq[{src, dst}]++}] = Msg{buf, bytes, false};
-    cv.notify_all();
-  }
-  void fetch(int src, int dst, void* out, size_t bytes)
-  {
-    std::unique_lock<std::mutex> g(m);
-    const long seq = recv_seq[{src, dst}]++;
-    cv.wait(g, [&] { return msgs.count({src, dst, seq}) != 0; });
-    Msg& msg = msgs[{src, dst, seq}];
-    if (msg.bytes != bytes) {
-      printf("loopback size mismatch %zu vs %zu\n", msg.bytes, bytes);
-      exit(1);
-    }
-    CHECK(hipMemcpy(out, msg.src, bytes, hipMemcpyDeviceToDevice));
-    msg.consumed = true;
-    cv.notify_all();
-  }
-  void drain(int src)
-  {
-    std::unique_lock<std::mutex> g(m);
-    cv.wait(g, [&] {
-      for (auto& kv : msgs)
-        if (std::get<0>(kv.first) == src && !kv.second.consumed) return false;
-      return true;
-    });
-  }
-};
-
-class LoopbackComm : public Communicator {
- public:
-  LoopbackComm(int rank, int size, Mailbox* mb) : mb_(mb)
-  {
-    mpi_rank = rank;
-    mpi_size = size;
-    current_device = 0;
-  }
-  void initialize() override {}
-  void start() override {}
-  void stop() override
-  {
-    mb_->drain(mpi_rank);
-    CHECK(hipDeviceSynchronize());
-  }
-  void send(const void* buf, int64_t count, int element_size, int dest) override
-  {
-    CHECK(hipDeviceSynchronize());
-    mb_->post(mpi_rank, dest, buf, (size_t)count * element_size);
-  }
-  void recv(void* buf, int64_t count, int element_size, int source) override
-  {
-    mb_->fetch(source, mpi_rank, buf, (size_t)count * element_size);
-  }
-  void finalize() override {}
-  bool group_by_batch() override { return true; }
-
- private:
-  Mailbox* mb_;
-};
 
 /* ---------------- tables ---------------- */
 
@@ -142,74 +51,30 @@ static uint64_t key_id(int64_t global_row, bool left)
 /* rows [row0, row0 + rows) of a global table as (key STRING, payload INT64) */
 static std::unique_ptr<cudf::table> make_table(int64_t row0, int64_t rows, bool left)
 {
-  std::vector<int32_t> off((size_t)rows + 1, 0);
-  std::string chars;
+  std::vector<std::string> key((size_t)rows);
   std::vector<int64_t> pay((size_t)rows);
   for (int64_t t = 0; t < rows; t++) {
-    chars += key_string(key_id(row0 + t, left));
-    off[(size_t)t + 1] = (int32_t)chars.size();
+    key[(size_t)t] = key_string(key_id(row0 + t, left));
     pay[(size_t)t] = (row0 + t) * 2 + (left ? 0 : 1);
   }
-  auto kcol = std::make_unique<cudf::column>((cudf::size_type)rows, (int64_t)chars.size());
-  CHECK(hipMemcpy(kcol->head(), off.data(), off.size() * 4, hipMemcpyHostToDevice));
-  if (!chars.empty())
-    CHECK(hipMemcpy(kcol->chars(), chars.data(), chars.size(), hipMemcpyHostToDevice));
-  auto pcol = std::make_unique<cudf::column>(cudf::data_type(cudf::type_id::INT64),
-                                             (cudf::size_type)rows);
-  if (rows) CHECK(hipMemcpy(pcol->head(), pay.data(), (size_t)rows * 8, hipMemcpyHostToDevice));
   std::vector<std::unique_ptr<cudf::column>> cols;
-  cols.push_back(std::move(kcol));
-  cols.push_back(std::move(pcol));
+  cols.push_back(device_strings(key));
+  cols.push_back(device_fixed(cudf::type_id::INT64, pay.data(), rows, 8));
   return std::make_unique<cudf::table>(std::move(cols));
-}
-
-static std::vector<std::string> strings_of(const cudf::column& col)
-{
-  const int64_t n = col.size();
-  std::vector<int32_t> off((size_t)n + 1);
-  CHECK(hipMemcpy(off.data(), col.head(), ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
-  std::string ch((size_t)col.chars_size(), '\0');
-  if (col.chars_size())
-    CHECK(hipMemcpy(&ch[0], col.chars(), (size_t)col.chars_size(), hipMemcpyDeviceToHost));
-  std::vector<std::string> out((size_t)n);
-  for (int64_t i = 0; i < n; i++)
-    out[(size_t)i] = ch.substr((size_t)off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i]));
-  return out;
-}
-
-static std::vector<int64_t> i64_of(const cudf::column& col)
-{
-  std::vector<int64_t> v((size_t)col.size());
-  if (col.size())
-    CHECK(hipMemcpy(v.data(), col.head(), (size_t)col.size() * 8, hipMemcpyDeviceToHost));
-  return v;
-}
-
-static uint64_t fold(const std::string& s)
-{
-  uint64_t h = 1469598103934665603ull ^ s.size();
-  for (unsigned char c : s) h = (h ^ c) * 1099511628211ull;
-  return h;
 }
 
 /* order-insensitive checksum over (STRING, INT64, STRING, INT64) join rows */
 static void checksum(const cudf::table& t, uint64_t* sum, int64_t* rows)
 {
   if (t.num_columns() != 4 || t.get_column(0).type().id() != cudf::type_id::STRING ||
-      t.get_column(2).type().id() != cudf::type_id::STRING) {
-    printf("JOIN OUTPUT SCHEMA WRONG\n");
-    exit(1);
-  }
-  auto lk = strings_of(t.get_column(0));
-  auto rk = strings_of(t.get_column(2));
-  auto lp = i64_of(t.get_column(1));
-  auto rp = i64_of(t.get_column(3));
+      t.get_column(2).type().id() != cudf::type_id::STRING)
+    FAIL("JOIN OUTPUT SCHEMA WRONG");
+  const HTable h = from_device(t);
+  const auto &lk = h[0].s, &rk = h[2].s;
+  const auto &lp = h[1].v, &rp = h[3].v;
   uint64_t s = 0;
   for (size_t i = 0; i < lk.size(); i++) {
-    if (lk[i] != rk[i]) {
-      printf("JOIN ROW WITH UNEQUAL KEYS\n");
-      exit(1);
-    }
+    if (lk[i] != rk[i]) FAIL("JOIN ROW WITH UNEQUAL KEYS");
     s += dj_mix64(fold(lk[i]) ^ dj_mix64((uint64_t)lp[i] ^
                                          dj_mix64((fold(rk[i]) + 1) ^ dj_mix64((uint64_t)rp[i]))));
   }
@@ -253,19 +118,13 @@ int main(int argc, char** argv)
   {
     Mailbox mb;
     std::vector<std::vector<std::string>> keys_on((size_t)G);
-    std::vector<std::thread> th;
-    for (int r = 0; r < G; r++) {
-      th.emplace_back([&, r] {
-        CHECK(hipSetDevice(0));
-        LoopbackComm comm(r, G, &mb);
-        auto t = make_table(r * per, per, true);
-        auto opts = generate_compression_options_distributed(t->view(), compress);
-        auto shuffled = shuffle_on(t->view(), {0}, &comm, opts, cudf::hash_id::HASH_MURMUR3,
-                                   12345678u);
-        keys_on[(size_t)r] = strings_of(shuffled->get_column(0));
-      });
-    }
-    for (auto& t : th) t.join();
+    run_ranks(G, &mb, [&](int r, Communicator* comm) {
+      auto t = make_table(r * per, per, true);
+      auto opts = generate_compression_options_distributed(t->view(), compress);
+      auto shuffled = shuffle_on(t->view(), {0}, comm, opts, cudf::hash_id::HASH_MURMUR3,
+                                 12345678u);
+      keys_on[(size_t)r] = from_device(shuffled->get_column(0)).s;
+    });
     std::map<std::string, int> owner;
     int64_t total = 0;
     for (int r = 0; r < G; r++) {
@@ -302,21 +161,15 @@ int main(int argc, char** argv)
     Mailbox mb;
     std::vector<uint64_t> sums((size_t)G, 0);
     std::vector<int64_t> rows((size_t)G, 0);
-    std::vector<std::thread> th;
-    for (int r = 0; r < G; r++) {
-      th.emplace_back([&, r] {
-        CHECK(hipSetDevice(0));
-        LoopbackComm comm(r, G, &mb);
-        auto left = make_table(r * per, per, true);
-        auto right = make_table(r * per, per, false);
-        auto lo = generate_compression_options_distributed(left->view(), compress);
-        auto ro = generate_compression_options_distributed(right->view(), compress);
-        auto res = distributed_inner_join(left->view(), right->view(), {0}, {0}, &comm, lo, ro,
-                                          2, false, nullptr, nvl);
-        checksum(*res, &sums[(size_t)r], &rows[(size_t)r]);
-      });
-    }
-    for (auto& t : th) t.join();
+    run_ranks(G, &mb, [&](int r, Communicator* comm) {
+      auto left = make_table(r * per, per, true);
+      auto right = make_table(r * per, per, false);
+      auto lo = generate_compression_options_distributed(left->view(), compress);
+      auto ro = generate_compression_options_distributed(right->view(), compress);
+      auto res = distributed_inner_join(left->view(), right->view(), {0}, {0}, comm, lo, ro,
+                                        2, false, nullptr, nvl);
+      checksum(*res, &sums[(size_t)r], &rows[(size_t)r]);
+    });
     uint64_t got_sum = 0;
     int64_t got_rows = 0;
     for (int r = 0; r < G; r++) {

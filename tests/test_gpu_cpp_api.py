@@ -12,6 +12,7 @@ import numpy as np
 import os
 import pytest
 
+import cpp_programs
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -114,16 +115,7 @@ def test_multirank_loopback():
     a user-style loopback Communicator (tests/cpp/multirank_loopback.cpp).
     Concatenated multi-rank result must equal the single-rank result."""
     import subprocess
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(repo, "tests", "cpp", "multirank_loopback")
-    if not os.path.exists(exe):
-        subprocess.run(
-            ["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17",
-             "-I", os.path.join(repo, "include"),
-             os.path.join(repo, "tests", "cpp", "multirank_loopback.cpp"),
-             "-o", exe, "-L", os.path.join(repo, "distributed_join_amd"), "-ldistjoin",
-             "-Wl,-rpath," + os.path.join(repo, "distributed_join_amd")],
-            check=True, capture_output=True)
+    exe = cpp_programs.build("multirank_loopback")
     # (G, over_decom, n_global, nvlink_domain_size, compression, reserved,
     #  key_mode); key_mode 1/2: heavily duplicated keys (1: one of them -1),
     # 3880 = 97 x 40 rows -> 97 x 40 x 40 = 155200 joined rows; key_mode 3:
@@ -181,9 +173,7 @@ def test_fused_big_buckets():
     shrinks the fan-out so 2 loopback ranks at 80M global rows reproduce the
     big-bucket regime (~2400 rows/bucket)."""
     import subprocess
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(repo, "tests", "cpp", "multirank_loopback")
-    assert os.path.exists(exe), "built by test_multirank_loopback"
+    exe = cpp_programs.build("multirank_loopback")
     for force_f in ("64", "1024"):
         # 64: ~2400 rows/bucket (4096-slot join); 1024: full fan-out, whose
         # sub-bucket bits must stay disjoint from the pass-A group bits

@@ -15,6 +15,7 @@ import sys
 import numpy as np
 import pytest
 
+import cpp_programs
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -546,16 +547,7 @@ def test_compressed_shuffle_typed_columns(dj, comm):
 # ------------------------------------------------------------- 7. multi-rank
 
 def test_dtype_loopback():
-    exe = os.path.join(REPO, "tests", "cpp", "dtype_loopback")
-    src = os.path.join(REPO, "tests", "cpp", "dtype_loopback.cpp")
-    if not os.path.exists(exe):
-        r = subprocess.run(
-            ["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17",
-             "-I", os.path.join(REPO, "include"), src, "-o", exe,
-             "-L", os.path.join(REPO, "distributed_join_amd"), "-ldistjoin",
-             "-Wl,-rpath,$ORIGIN/../../distributed_join_amd"],
-            capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
+    exe = cpp_programs.build("dtype_loopback")
     # (G, nvlink_domain_size, compression); G = 3 gives odd slice boundaries
     for args in (["3", "3", "0"], ["4", "1", "0"], ["2", "2", "1"]):
         r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=240)

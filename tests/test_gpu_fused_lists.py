@@ -12,11 +12,9 @@ import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(REPO, "tests", "cpp", "fused_lists_check.cpp")
-EXE = os.path.join(REPO, "tests", "cpp", "fused_lists_check")
-LIB = os.path.join(REPO, "distributed_join_amd", "libdistjoin.so")
-CSRC = os.path.join(REPO, "distributed_join_amd", "csrc")
+import cpp_programs
+
+LIB = cpp_programs.LIB
 
 # 15 fused_partition runs (6 shapes, 6 sizes, second seed, null payload, equal
 # keys), 5 hand-built segment lists, the chained case's 2 partitions + 1 list
@@ -24,15 +22,7 @@ RUNS = 23
 
 
 def _harness():
-    deps = [SRC, LIB] + [os.path.join(CSRC, h) for h in ("dj_kernels.hpp", "dj_rng.h", "dj_hash.h")]
-    if not os.path.exists(EXE) or any(
-            os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
-        subprocess.run(
-            ["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-I", CSRC, SRC,
-             "-o", EXE, "-L", os.path.dirname(LIB), "-ldistjoin",
-             "-Wl,-rpath," + os.path.dirname(LIB)],
-            check=True, capture_output=True)
-    return EXE
+    return cpp_programs.build("fused_lists_check", include=("csrc",))
 
 
 @pytest.mark.gpu

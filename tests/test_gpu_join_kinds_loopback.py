@@ -2,34 +2,20 @@
 over a counting loopback Communicator (tests/cpp/joinkinds_loopback.cpp),
 every result against a host join of the global tables; the semi join's wire
 bytes do not depend on the right table's payload columns."""
-import os
 import subprocess
 
 import pytest
 
-pytestmark = pytest.mark.gpu
+import cpp_programs
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def exe():
     import distributed_join_amd as dj
     dj.require_gpu()
-    exe = os.path.join(REPO, "tests", "cpp", "joinkinds_loopback")
-    src = os.path.join(REPO, "tests", "cpp", "joinkinds_loopback.cpp")
-    # rebuilt whenever the source or the library is newer than the program
-    newest = max(os.path.getmtime(src),
-                 os.path.getmtime(os.path.join(REPO, "distributed_join_amd", "libdistjoin.so")))
-    if not os.path.exists(exe) or os.path.getmtime(exe) < newest:
-        r = subprocess.run(
-            ["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17",
-             "-I", os.path.join(REPO, "include"), src, "-o", exe,
-             "-L", os.path.join(REPO, "distributed_join_amd"), "-ldistjoin",
-             "-Wl,-rpath,$ORIGIN/../../distributed_join_amd"],
-            capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return cpp_programs.build("joinkinds_loopback")
 
 
 @pytest.mark.parametrize("G", [2, 3, 8])

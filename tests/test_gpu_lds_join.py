@@ -10,11 +10,9 @@ import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(REPO, "tests", "cpp", "lds_join_check.cpp")
-EXE = os.path.join(REPO, "tests", "cpp", "lds_join_check")
-LIB = os.path.join(REPO, "distributed_join_amd", "libdistjoin.so")
-CSRC = os.path.join(REPO, "distributed_join_amd", "csrc")
+import cpp_programs
+
+LIB = cpp_programs.LIB
 
 # 62 cases (2 build-length edge, 2 table reset, 20 + 30 stage arithmetic,
 # 2 wrap-around, 3 duplicates/sentinel, 3 second trip), each in both layouts
@@ -22,15 +20,7 @@ RUNS = 124
 
 
 def _harness():
-    deps = [SRC, LIB, os.path.join(CSRC, "dj_kernels.hpp"), os.path.join(CSRC, "dj_rng.h")]
-    if not os.path.exists(EXE) or any(
-            os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
-        subprocess.run(
-            ["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-I", CSRC, SRC,
-             "-o", EXE, "-L", os.path.dirname(LIB), "-ldistjoin",
-             "-Wl,-rpath," + os.path.dirname(LIB)],
-            check=True, capture_output=True)
-    return EXE
+    return cpp_programs.build("lds_join_check", include=("csrc",))
 
 
 @pytest.mark.gpu

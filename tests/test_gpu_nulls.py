@@ -18,6 +18,8 @@ from collections import defaultdict
 import numpy as np
 import pytest
 
+import cpp_programs
+
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -613,19 +615,7 @@ def test_null_loopback(dj, G, rows):
     (tests/cpp/null_loopback.cpp): shuffle and joins of nullable tables against
     a host reference, one rank passing a column without a mask; the mask-free
     tables see the recorded send/recv calls and bytes."""
-    exe = os.path.join(REPO, "tests", "cpp", "null_loopback")
-    src = os.path.join(REPO, "tests", "cpp", "null_loopback.cpp")
-    # rebuilt whenever the source or the library is newer than the program
-    newest = max(os.path.getmtime(src),
-                 os.path.getmtime(os.path.join(REPO, "distributed_join_amd", "libdistjoin.so")))
-    if not os.path.exists(exe) or os.path.getmtime(exe) < newest:
-        r = subprocess.run(
-            ["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17",
-             "-I", os.path.join(REPO, "include"), src, "-o", exe,
-             "-L", os.path.join(REPO, "distributed_join_amd"), "-ldistjoin",
-             "-Wl,-rpath,$ORIGIN/../../distributed_join_amd"],
-            capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
+    exe = cpp_programs.build("null_loopback")
     r = subprocess.run([exe, str(G), str(rows)], capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count("NULL LOOPBACK OK") == 1, r.stdout

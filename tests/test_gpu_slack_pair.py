@@ -13,11 +13,9 @@ import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(REPO, "tests", "cpp", "slack_pair_check.cpp")
-EXE = os.path.join(REPO, "tests", "cpp", "slack_pair_check")
-LIB = os.path.join(REPO, "distributed_join_amd", "libdistjoin.so")
-CSRC = os.path.join(REPO, "distributed_join_amd", "csrc")
+import cpp_programs
+
+LIB = cpp_programs.LIB
 
 # runs (": ok" lines) and cases per set; "special keys" and one pass-B edge run twice
 SETS = {
@@ -34,15 +32,7 @@ CASES = sum(cases for _, cases in SETS.values())
 
 
 def _harness():
-    deps = [SRC, LIB, os.path.join(CSRC, "dj_kernels.hpp"), os.path.join(CSRC, "dj_rng.h")]
-    if not os.path.exists(EXE) or any(
-            os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
-        subprocess.run(
-            ["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-I", CSRC, SRC,
-             "-o", EXE, "-L", os.path.dirname(LIB), "-ldistjoin",
-             "-Wl,-rpath," + os.path.dirname(LIB)],
-            check=True, capture_output=True)
-    return EXE
+    return cpp_programs.build("slack_pair_check", include=("csrc",))
 
 
 @pytest.mark.gpu

@@ -18,6 +18,7 @@ import sys
 import numpy as np
 import pytest
 
+import cpp_programs
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -445,16 +446,7 @@ def test_stringkey_loopback(dj):
     (tests/cpp/stringkey_loopback.cpp): after shuffle_on every distinct key
     string lives on one rank; the concatenated distributed_inner_join equals
     the single-rank result."""
-    exe = os.path.join(REPO, "tests", "cpp", "stringkey_loopback")
-    src = os.path.join(REPO, "tests", "cpp", "stringkey_loopback.cpp")
-    if not os.path.exists(exe):
-        r = subprocess.run(
-            ["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17",
-             "-I", os.path.join(REPO, "include"), src, "-o", exe,
-             "-L", os.path.join(REPO, "distributed_join_amd"), "-ldistjoin",
-             "-Wl,-rpath,$ORIGIN/../../distributed_join_amd"],
-            capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
+    exe = cpp_programs.build("stringkey_loopback")
     # (G, nvlink_domain_size, compression)
     for args in (["2", "2", "0"], ["4", "4", "0"],
                  ["4", "2", "0"],    # 2-level hierarchy
