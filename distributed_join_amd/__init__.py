@@ -128,6 +128,10 @@ def lib():
             "dj_copy_bitmask_segments": ([vp, vp, vp, i32, vp], i64),
             "dj_cpp_distributed_join_ncols_multi": ([vp, i32, vp, i32, i64, vp, i32, i64,
                                                      vp, vp, i32, i32, i32], vp),
+            "dj_cpp_distributed_join_ncols_multi_ne": ([vp, i32, i32, vp, i32, i64, vp, i32, i64,
+                                                        vp, vp, i32, i32, i32], vp),
+            "dj_key_row_validity": ([vp, i32, i64, vp], i64),
+            "dj_compact_keyed_rows": ([vp, i64, vp, vp, vp, i32, vp], i64),
             "dj_mark_rows": ([vp, i64, vp, i32, i32, vp], None),
             "dj_select_rows": ([vp, i64, i32, vp, i32, vp], i64),
             "dj_select_rows_tile_rows": ([], i64),
@@ -761,20 +765,34 @@ def copy_bitmask_segments(segments, fill=0xFFFFFFFF):
 JOIN_INNER, JOIN_LEFT, JOIN_LEFT_SEMI, JOIN_LEFT_ANTI = 0, 1, 2, 3
 
 
+# null_equality of include/dj_cudf_types.hpp, as the C ABI passes it
+# (DJ_NULL_EQUAL / DJ_NULL_UNEQUAL)
+NULL_EQUAL, NULL_UNEQUAL = 0, 1
+
+
 def cpp_distributed_join_ncols_multi(comm, kind, lcols, ln, rcols, rn, left_on, right_on,
-                                     over_decom=1):
+                                     over_decom=1, null_equality=NULL_EQUAL):
     """distributed_join of the given kind (JOIN_*) over nullable column
     descriptors, as cpp_distributed_inner_join_ncols_multi takes them.
     JOIN_LEFT returns left then right columns, every right-hand column with a
     mask; JOIN_LEFT_SEMI / JOIN_LEFT_ANTI return the left columns only.
+    null_equality: NULL_EQUAL, a null key element matches a null one, or
+    NULL_UNEQUAL (SQL), a row with a null in its key tuple matches nothing;
+    any other value raises ValueError.
     Returns (cols, masks) as table_to_numpy_nullable."""
+    if null_equality not in (NULL_EQUAL, NULL_UNEQUAL) or isinstance(null_equality, bool):
+        raise ValueError(f"null_equality must be NULL_EQUAL or NULL_UNEQUAL, not {null_equality!r}")
     la, ra = _pack_ncols(lcols), _pack_ncols(rcols)
     lon = np.asarray(left_on, dtype=np.int32)
     ron = np.asarray(right_on, dtype=np.int32)
-    t = lib().dj_cpp_distributed_join_ncols_multi(
-        comm.ptr, int(kind), ctypes.cast(la, ctypes.c_void_p), len(lcols), ln,
-        ctypes.cast(ra, ctypes.c_void_p), len(rcols), rn,
-        lon.ctypes.data, ron.ctypes.data, len(lon), over_decom, 0)
+    tables = (ctypes.cast(la, ctypes.c_void_p), len(lcols), ln,
+              ctypes.cast(ra, ctypes.c_void_p), len(rcols), rn,
+              lon.ctypes.data, ron.ctypes.data, len(lon), over_decom, 0)
+    if null_equality == NULL_EQUAL:
+        t = lib().dj_cpp_distributed_join_ncols_multi(comm.ptr, int(kind), *tables)
+    else:
+        t = lib().dj_cpp_distributed_join_ncols_multi_ne(comm.ptr, int(kind),
+                                                         int(null_equality), *tables)
     return table_to_numpy_nullable(t)
 
 
@@ -799,6 +817,30 @@ def select_rows(d_bits_ptr, nrows, want_set, d_out_ptr, reps=1):
     count = lib().dj_select_rows(d_bits_ptr, nrows, int(bool(want_set)), d_out_ptr, reps,
                                  ms.ctypes.data)
     return int(count), ms
+
+
+def compact_keyed_rows(d_bits_ptr, nrows, d_keys_ptr, d_out_idx_ptr, d_out_keys_ptr, reps=1):
+    """The keyed compaction through its test/bench hook: select_rows for the
+    set bits that also writes out_keys[k] = keys[out_idx[k]] (both outputs:
+    room for as many int64 as are selected). Returns (count, per-repetition
+    ms)."""
+    ms = np.zeros(max(reps, 1), dtype=np.float64)
+    count = lib().dj_compact_keyed_rows(d_bits_ptr, nrows, d_keys_ptr, d_out_idx_ptr,
+                                        d_out_keys_ptr, reps, ms.ctypes.data)
+    return int(count), ms
+
+
+def key_row_validity(mask_ptrs, nrows, d_out_ptr):
+    """The row validity of a key tuple through its test/bench hook: the AND
+    of the 1..4 device masks in mask_ptrs (None = all valid) into the
+    ceil(nrows / 32) words at d_out_ptr, bits at and past nrows as 0. Returns
+    the number of 0 bits among nrows."""
+    nm = len(mask_ptrs)
+    if not 1 <= nm <= 4:
+        raise ValueError("key_row_validity takes 1 to 4 masks")
+    src = (ctypes.c_void_p * nm)(*[m if m else None for m in mask_ptrs])
+    return int(lib().dj_key_row_validity(ctypes.cast(src, ctypes.c_void_p), nm, nrows,
+                                         d_out_ptr))
 
 
 def select_rows_tile_rows():

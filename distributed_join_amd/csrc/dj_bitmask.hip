@@ -8,6 +8,8 @@
  *   copy_bitmask_segments  concatenate bit ranges cut at arbitrary bit
  *                          offsets into one destination mask
  *   count_unset_bits       nulls among the first n bits of a mask
+ *   key_row_validity       the AND of up to 4 masks (the rows of a key tuple
+ *                          that hold no null) and the number of its 0 bits
  *
  * No kernel here does a read-modify-write or an atomic on a mask word: every
  * destination word is built whole by one lane and stored once. Bits past the
@@ -148,6 +150,42 @@ __global__ __launch_bounds__(kMaskBlock) void count_unset_bits_kernel(
   if (threadIdx.x == 0 && s_sum) atomicAdd(out, (unsigned long long)s_sum);
 }
 
+/* the masks of a key tuple's columns; nullptr = that column is all valid */
+struct KeyMasks {
+  const uint32_t* m[kMaxKeyMasks];
+  int n;
+};
+
+/* Thread w builds destination word w: the AND of word w of every mask that is
+ * there, cut to the rows below nrows, stored once. Reads (masks present) x
+ * nrows / 8 bytes and writes nrows / 8; the 0 bits among nrows are summed per
+ * wave, per block in LDS, and leave as one global atomicAdd per block onto
+ * the counter (never onto a mask word). */
+__global__ __launch_bounds__(kMaskBlock) void key_row_validity_kernel(
+  KeyMasks km, int64_t nrows, int64_t nwords, uint32_t* __restrict__ dst,
+  unsigned long long* __restrict__ nulls)
+{
+  __shared__ uint32_t s_sum;
+  if (threadIdx.x == 0) s_sum = 0;
+  __syncthreads();
+  uint32_t acc = 0;
+  int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; w < nwords; w += stride) {
+    const int64_t rem = nrows - w * 32;
+    const uint32_t live = rem >= 32 ? 0xFFFFFFFFu : ((1u << (int)rem) - 1u);
+    uint32_t v = live;
+    for (int c = 0; c < km.n; c++)
+      if (km.m[c] != nullptr) v &= km.m[c][w];
+    dst[w] = v;
+    acc += (uint32_t)__popc(~v & live);
+  }
+  for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+  if ((threadIdx.x & (kWave - 1)) == 0 && acc) atomicAdd(&s_sum, acc);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_sum) atomicAdd(nulls, (unsigned long long)s_sum);
+}
+
 int mask_grid(int64_t items_per_thread_domain)
 {
   int64_t blocks = (items_per_thread_domain + kMaskBlock - 1) / kMaskBlock;
@@ -215,6 +253,22 @@ void count_unset_bits(const uint32_t* d_mask, int64_t n, unsigned long long* d_c
   const int64_t nwords = (n + 31) / 32;
   hipLaunchKernelGGL(count_unset_bits_kernel, dim3(mask_grid(nwords)), dim3(kMaskBlock), 0, s,
                      d_mask, n, nwords, d_count);
+  DJ_HIP_CALL(hipGetLastError());
+}
+
+void key_row_validity(const uint32_t* const* masks, int nmasks, int64_t nrows, uint32_t* d_out,
+                      unsigned long long* d_null_count, hipStream_t s)
+{
+  DJ_CHECK_ERROR(nmasks >= 1 && nmasks <= kMaxKeyMasks, "key_row_validity: 1..4 masks");
+  if (nrows <= 0) return;
+  DJ_CHECK_ERROR(masks != nullptr && d_out != nullptr && d_null_count != nullptr,
+                 "key_row_validity: null pointer");
+  KeyMasks km{};
+  km.n = nmasks;
+  for (int c = 0; c < nmasks; c++) km.m[c] = masks[c];
+  const int64_t nwords = (nrows + 31) / 32;
+  hipLaunchKernelGGL(key_row_validity_kernel, dim3(mask_grid(nwords)), dim3(kMaskBlock), 0, s, km,
+                     nrows, nwords, d_out, d_null_count);
   DJ_HIP_CALL(hipGetLastError());
 }
 

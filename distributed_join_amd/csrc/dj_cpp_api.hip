@@ -1992,6 +1992,77 @@ dj::TupleKeyCol tuple_key_col(cudf::column_view col)
   return d;
 }
 
+/* ---- null_equality::UNEQUAL: a row with a null anywhere in its key tuple
+ * matches nothing, so it never enters the engine ---- */
+
+/* which rows of a table hold no null in their key tuple */
+struct KeyRowValidity {
+  DBuf own;                       // the AND of the key masks, where it had to be built
+  const uint32_t* bits{nullptr};  // 1 = no null in the tuple; nullptr: every row
+  int64_t nnull{0};               // rows with a null in their tuple
+};
+
+/* Only the key columns that may hold a null take part. With exactly one, that
+ * column's mask IS the row validity (select_rows and compact_keyed_rows
+ * ignore its bits past the row count) and only its nulls are counted.
+ * Host-synchronous when a mask takes part. */
+KeyRowValidity key_row_validity(cudf::table_view t, std::vector<cudf::size_type> const& on,
+                                hipStream_t st)
+{
+  KeyRowValidity v;
+  const uint32_t* masks[dj::kMaxKeyMasks];
+  int nm = 0;
+  for (auto c : on) {
+    cudf::column_view col = t.column(c);
+    if (!col.nullable() || col.null_count() == 0) continue;
+    DJ_CHECK_ERROR(nm < dj::kMaxKeyMasks, "up to 4 join key columns supported");
+    masks[nm++] = col.null_mask();
+  }
+  const int64_t n = t.num_rows();
+  if (nm == 0 || n == 0) return v;
+  /* the number of null-key rows sizes the compacted arrays, so it is counted
+   * from the bits here and not taken from a view's null_count */
+  DBuf cnt(8);
+  DJ_HIP_CALL(hipMemsetAsync(cnt.p, 0, 8, st));
+  if (nm == 1) {
+    dj::count_unset_bits(masks[0], n, (unsigned long long*)cnt.p, st);
+  } else {
+    v.own = DBuf((size_t)((n + 31) / 32) * 4);
+    dj::key_row_validity(masks, nm, n, (uint32_t*)v.own.p, (unsigned long long*)cnt.p, st);
+  }
+  unsigned long long h = 0;
+  DJ_HIP_CALL(hipMemcpyAsync(&h, cnt.p, 8, hipMemcpyDeviceToHost, st));
+  DJ_HIP_CALL(hipStreamSynchronize(st));
+  v.nnull = (int64_t)h;
+  if (v.nnull > 0) v.bits = nm == 1 ? masks[0] : (const uint32_t*)v.own.p;
+  return v;
+}
+
+/* the engine's view of one side under UNEQUAL: the keys of the valid-key
+ * rows and, as the payload, their row numbers in the table */
+struct CompactedKeys {
+  DBuf keys, rows;
+  int64_t n{0};
+};
+
+CompactedKeys compact_valid_keys(KeyRowValidity const& v, const int64_t* keys, int64_t nrows,
+                                 hipStream_t st)
+{
+  CompactedKeys c;
+  c.n = nrows - v.nnull;
+  if (c.n <= 0) return c;
+  c.keys = DBuf((size_t)c.n * 8);
+  c.rows = DBuf((size_t)c.n * 8);
+  DBuf scratch(dj::select_rows_scratch_bytes(nrows)), count(8);
+  dj::compact_keyed_rows(v.bits, nrows, keys, c.rows.i64(), c.keys.i64(), count.i64(), st,
+                         scratch.p);
+  int64_t got = 0;
+  DJ_HIP_CALL(hipMemcpyAsync(&got, count.p, 8, hipMemcpyDeviceToHost, st));
+  DJ_HIP_CALL(hipStreamSynchronize(st));
+  DJ_CHECK_ERROR(got == c.n, "join: a key column's null_count disagrees with its mask");
+  return c;
+}
+
 /* local join of two tables via the bucketed-LDS engine. INNER returns
  * left-cols + right-cols with keys duplicated, row order unspecified; the
  * other kinds build the same pair list and hand it to assemble_left_kind.
@@ -2002,12 +2073,13 @@ dj::TupleKeyCol tuple_key_col(cudf::column_view col)
  * columns — the single-key engine does the heavy lifting; only
  * placement/equality semantics widen. (Reference: cudf::inner_join on
  * arbitrary left_on/right_on, distributed_join.cpp:71-132.) */
-std::unique_ptr<cudf::table> local_join(join_kind kind, cudf::table_view left,
-                                        cudf::table_view right,
-                                        std::vector<cudf::size_type> const& lon,
-                                        std::vector<cudf::size_type> const& ron)
+std::unique_ptr<cudf::table> local_join(
+  join_kind kind, cudf::table_view left, cudf::table_view right,
+  std::vector<cudf::size_type> const& lon, std::vector<cudf::size_type> const& ron,
+  cudf::null_equality compare_nulls = cudf::null_equality::EQUAL)
 {
   const bool inner = kind == join_kind::INNER;
+  const bool sql = compare_nulls == cudf::null_equality::UNEQUAL;
   DJ_CHECK_ERROR(lon.size() == ron.size(), "left_on/right_on must have equal length");
   bool str_keys = false;
   for (size_t c = 0; c < lon.size(); c++) {
@@ -2015,18 +2087,30 @@ std::unique_ptr<cudf::table> local_join(join_kind kind, cudf::table_view left,
     DJ_CHECK_ERROR(ls == rs, "a STRING key column must pair with a STRING key column");
     str_keys |= ls;
   }
-  /* nullable keys take the fused route too: fuse_keys gives every null
-   * element one constant, so all-null tuples meet in the bucket join, and the
-   * tuple filter applies null_equality::EQUAL against the masks */
-  const bool fused = lon.size() > 1 || str_keys || any_nullable_key(left, lon) ||
-                     any_nullable_key(right, ron);
+  /* under null_equality::EQUAL nullable keys take the fused route too:
+   * fuse_keys gives every null element one constant, so all-null tuples meet
+   * in the bucket join, and the tuple filter applies EQUAL against the masks.
+   * Under UNEQUAL the null-key rows stay out of the engine (below), so a
+   * single integer key runs unfused whatever its mask; composite and STRING
+   * keys still fuse, and every tuple their filter sees is fully valid. */
+  const bool fused = lon.size() > 1 || str_keys ||
+                     (!sql && (any_nullable_key(left, lon) || any_nullable_key(right, ron)));
   hipStream_t st = dj_rt_stream();
   const int64_t ln = left.num_rows(), rn = right.num_rows();
-  if (ln == 0 || rn == 0) {
+  /* no pair list to build: every left row (if any) is unmatched */
+  auto no_pairs = [&]() {
     if (inner) return empty_join_result(left, right);  // distributed_join.cpp:76-83
-    /* no pair list to build: every left row (if any) is unmatched */
     JoinOut none;
     return assemble_left_kind(kind, left, right, none, 0, 0);
+  };
+  if (ln == 0 || rn == 0) return no_pairs();
+  /* UNEQUAL: the rows of each side that hold a null in their key tuple. A
+   * side left with no valid-key row is an empty side. */
+  KeyRowValidity lvalid, rvalid;
+  if (sql) {
+    lvalid = key_row_validity(left, lon, st);
+    rvalid = key_row_validity(right, ron, st);
+    if (lvalid.nnull == ln || rvalid.nnull == rn) return no_pairs();
   }
 
   /* the output's key columns: known only for a single integer key (a fused
@@ -2052,8 +2136,27 @@ std::unique_ptr<cudf::table> local_join(join_kind kind, cudf::table_view left,
   const bool pairs = inner && joins_i64_pairs(left, right, left_key, right_key);
   const int64_t* lp = pairs ? left.column(1).head<int64_t>() : nullptr;
   const int64_t* rp = pairs ? right.column(1).head<int64_t>() : nullptr;
+  /* UNEQUAL with null keys: the engine joins the keys of the valid-key rows
+   * and carries their row numbers as the payload, so the pair list comes back
+   * in row numbers of the original tables: no column is compacted, the null
+   * rows of the left stay unmarked (LEFT pads them, LEFT_ANTI keeps them)
+   * and those of the right are in no pair */
+  int64_t eln = ln, ern = rn;
+  CompactedKeys lc, rc;
+  if (lvalid.nnull > 0) {
+    lc = compact_valid_keys(lvalid, lk, ln, st);
+    lk = lc.keys.i64();
+    lp = lc.rows.i64();
+    eln = lc.n;
+  }
+  if (rvalid.nnull > 0) {
+    rc = compact_valid_keys(rvalid, rk, rn, st);
+    rk = rc.keys.i64();
+    rp = rc.rows.i64();
+    ern = rc.n;
+  }
 
-  auto joined = run_bucket_join(lk, lp, ln, rk, rp, rn);
+  auto joined = run_bucket_join(lk, lp, eln, rk, rp, ern);
   JoinOut& out = joined.first;
   int64_t nout = joined.second;
   int64_t li_cap = out.cap;  // elements the left-index array has room for
@@ -2090,6 +2193,49 @@ std::unique_ptr<cudf::table> local_inner_join(cudf::table_view left, cudf::table
                                               std::vector<cudf::size_type> const& ron)
 {
   return local_join(join_kind::INNER, left, right, lon, ron);
+}
+
+/* null_equality::UNEQUAL over several ranks: a table cut, before anything is
+ * communicated, into `valid`, its rows without a null in their key tuple
+ * (same schema, mask presence included), and, when asked for, `null_rows`,
+ * the others in the form the rank appends to its result: the table's columns
+ * and, with pad_with, behind them that table's columns as all-null cells, as
+ * a LEFT join pads an unmatched row. Both are null when no key column holds
+ * a null: the caller goes on with the table it has. One full gather of the
+ * table through the ascending row list of select_rows. */
+struct StrippedTable {
+  std::unique_ptr<cudf::table> valid, null_rows;
+};
+
+StrippedTable strip_null_keys(cudf::table_view t, std::vector<cudf::size_type> const& on,
+                              bool keep_null_rows, const cudf::table_view* pad_with)
+{
+  hipStream_t st = dj_rt_stream();
+  StrippedTable out;
+  const int64_t n = t.num_rows();
+  KeyRowValidity v = key_row_validity(t, on, st);
+  if (v.nnull == 0) return out;
+  DBuf scratch(dj::select_rows_scratch_bytes(n)), count(8);
+  auto take = [&](bool want_set, int64_t expect, const cudf::table_view* pad) {
+    std::vector<std::unique_ptr<cudf::column>> cols;
+    if (expect == 0) {
+      append_empty_columns(t, false, cols);
+      if (pad) append_empty_columns(*pad, true, cols);
+      return std::make_unique<cudf::table>(std::move(cols));
+    }
+    DBuf sel((size_t)expect * 8);
+    dj::select_rows(v.bits, n, want_set, sel.i64(), count.i64(), st, scratch.p);
+    gather_table_columns(t, sel, expect, -1, nullptr, cols, st);
+    if (pad) {
+      DBuf none;
+      gather_table_columns(*pad, none, 0, -1, nullptr, cols, st, expect);
+    }
+    DJ_HIP_CALL(hipStreamSynchronize(st));
+    return std::make_unique<cudf::table>(std::move(cols));
+  };
+  out.valid = take(true, n - v.nnull, nullptr);
+  if (keep_null_rows) out.null_rows = take(false, v.nnull, pad_with);
+  return out;
 }
 
 /* rebase a part's offsets by a constant and append (STRING concat) */
@@ -2664,15 +2810,17 @@ std::unique_ptr<cudf::table> distributed_join(
   int over_decom_factor,
   bool report_timing,
   void* preallocated_pinned_buffer,
-  int nvlink_domain_size)
+  int nvlink_domain_size,
+  cudf::null_equality compare_nulls)
 {
-  if (kind == join_kind::INNER)
+  const bool sql = compare_nulls == cudf::null_equality::UNEQUAL;
+  if (kind == join_kind::INNER && !sql)
     return distributed_inner_join(left, right, left_on, right_on, communicator,
                                   std::move(left_compression_options),
                                   std::move(right_compression_options), over_decom_factor,
                                   report_timing, preallocated_pinned_buffer, nvlink_domain_size);
-  DJ_CHECK_ERROR(kind == join_kind::LEFT || kind == join_kind::LEFT_SEMI ||
-                   kind == join_kind::LEFT_ANTI,
+  DJ_CHECK_ERROR(kind == join_kind::INNER || kind == join_kind::LEFT ||
+                   kind == join_kind::LEFT_SEMI || kind == join_kind::LEFT_ANTI,
                  "distributed_join: unknown join kind");
   DJ_CHECK_ERROR(left_on.size() == right_on.size() && !left_on.empty(),
                  "left_on/right_on must name the same number of key columns");
@@ -2684,7 +2832,7 @@ std::unique_ptr<cudf::table> distributed_join(
   /* a semi / anti join asks of the right table only whether a key exists:
    * its other columns stay home, before any stage that communicates */
   std::vector<cudf::size_type> ron = right_on;
-  if (kind != join_kind::LEFT) {
+  if (kind == join_kind::LEFT_SEMI || kind == join_kind::LEFT_ANTI) {
     std::vector<cudf::column_view> key_cols;
     std::vector<ColumnCompressionOptions> key_opts;
     for (size_t k = 0; k < right_on.size(); k++) {
@@ -2699,6 +2847,34 @@ std::unique_ptr<cudf::table> distributed_join(
   }
 
   const int world = communicator->mpi_size;
+  /* one rank: the local join keeps the null-key rows out of the engine
+   * itself, without compacting a column */
+  if (world == 1) return local_join(kind, left, right, left_on, ron, compare_nulls);
+
+  /* null_equality::UNEQUAL over several ranks: null-key rows never reach the
+   * communicator. Each rank strips its tables to their valid-key rows before
+   * the first stage that communicates (a local step that leaves the schema,
+   * mask presence included, as it is, so the route and its tag are those of
+   * the EQUAL join of the stripped tables) and, for LEFT and LEFT_ANTI,
+   * appends its own null-key left rows to its result. */
+  if (sql) {
+    const bool keep = kind == join_kind::LEFT || kind == join_kind::LEFT_ANTI;
+    StrippedTable l =
+      strip_null_keys(left, left_on, keep, kind == join_kind::LEFT ? &right : nullptr);
+    StrippedTable r = strip_null_keys(right, ron, false, nullptr);
+    if (l.valid) left = l.valid->view();
+    if (r.valid) right = r.valid->view();
+    auto joined =
+      distributed_join(kind, left, right, left_on, ron, communicator, left_compression_options,
+                       right_compression_options, over_decom_factor, report_timing,
+                       preallocated_pinned_buffer, nvlink_domain_size);
+    if (!l.null_rows) return joined;
+    std::vector<std::unique_ptr<cudf::table>> parts;
+    parts.push_back(std::move(joined));
+    parts.push_back(std::move(l.null_rows));
+    return concat_tables(parts);
+  }
+
   const int nvl = get_nvl_partition_size(world, nvlink_domain_size < 1 ? 1 : nvlink_domain_size);
   /* the same inter-domain stage as the inner join's (seed 87654321) */
   std::unique_ptr<cudf::table> l_ib, r_ib;
@@ -2735,12 +2911,14 @@ std::unique_ptr<cudf::table> distributed_left_join(
   std::vector<cudf::size_type> const& right_on, Communicator* communicator,
   std::vector<ColumnCompressionOptions> left_compression_options,
   std::vector<ColumnCompressionOptions> right_compression_options, int over_decom_factor,
-  bool report_timing, void* preallocated_pinned_buffer, int nvlink_domain_size)
+  bool report_timing, void* preallocated_pinned_buffer, int nvlink_domain_size,
+  cudf::null_equality compare_nulls)
 {
   return distributed_join(join_kind::LEFT, left, right, left_on, right_on, communicator,
                           std::move(left_compression_options),
                           std::move(right_compression_options), over_decom_factor,
-                          report_timing, preallocated_pinned_buffer, nvlink_domain_size);
+                          report_timing, preallocated_pinned_buffer, nvlink_domain_size,
+                          compare_nulls);
 }
 
 std::unique_ptr<cudf::table> distributed_left_semi_join(
@@ -2748,12 +2926,14 @@ std::unique_ptr<cudf::table> distributed_left_semi_join(
   std::vector<cudf::size_type> const& right_on, Communicator* communicator,
   std::vector<ColumnCompressionOptions> left_compression_options,
   std::vector<ColumnCompressionOptions> right_compression_options, int over_decom_factor,
-  bool report_timing, void* preallocated_pinned_buffer, int nvlink_domain_size)
+  bool report_timing, void* preallocated_pinned_buffer, int nvlink_domain_size,
+  cudf::null_equality compare_nulls)
 {
   return distributed_join(join_kind::LEFT_SEMI, left, right, left_on, right_on, communicator,
                           std::move(left_compression_options),
                           std::move(right_compression_options), over_decom_factor,
-                          report_timing, preallocated_pinned_buffer, nvlink_domain_size);
+                          report_timing, preallocated_pinned_buffer, nvlink_domain_size,
+                          compare_nulls);
 }
 
 std::unique_ptr<cudf::table> distributed_left_anti_join(
@@ -2761,12 +2941,14 @@ std::unique_ptr<cudf::table> distributed_left_anti_join(
   std::vector<cudf::size_type> const& right_on, Communicator* communicator,
   std::vector<ColumnCompressionOptions> left_compression_options,
   std::vector<ColumnCompressionOptions> right_compression_options, int over_decom_factor,
-  bool report_timing, void* preallocated_pinned_buffer, int nvlink_domain_size)
+  bool report_timing, void* preallocated_pinned_buffer, int nvlink_domain_size,
+  cudf::null_equality compare_nulls)
 {
   return distributed_join(join_kind::LEFT_ANTI, left, right, left_on, right_on, communicator,
                           std::move(left_compression_options),
                           std::move(right_compression_options), over_decom_factor,
-                          report_timing, preallocated_pinned_buffer, nvlink_domain_size);
+                          report_timing, preallocated_pinned_buffer, nvlink_domain_size,
+                          compare_nulls);
 }
 
 
@@ -3371,14 +3553,30 @@ void* dj_cpp_distributed_join_ncols_multi(void* comm, int kind, const dj_ncol_de
                                           int64_t rn, const int32_t* lon, const int32_t* ron,
                                           int nkeys, int over_decom, int report_timing)
 {
+  return dj_cpp_distributed_join_ncols_multi_ne(comm, kind, DJ_NULL_EQUAL, lcols, nl, ln, rcols,
+                                                nr, rn, lon, ron, nkeys, over_decom,
+                                                report_timing);
+}
+
+void* dj_cpp_distributed_join_ncols_multi_ne(void* comm, int kind, int null_equality,
+                                             const dj_ncol_desc* lcols, int nl, int64_t ln,
+                                             const dj_ncol_desc* rcols, int nr, int64_t rn,
+                                             const int32_t* lon, const int32_t* ron, int nkeys,
+                                             int over_decom, int report_timing)
+{
   DJ_CHECK_ERROR(kind >= DJ_JOIN_INNER && kind <= DJ_JOIN_LEFT_ANTI, "join kind must be 0..3");
+  DJ_CHECK_ERROR(null_equality == DJ_NULL_EQUAL || null_equality == DJ_NULL_UNEQUAL,
+                 "null_equality must be DJ_NULL_EQUAL (0) or DJ_NULL_UNEQUAL (1)");
   auto left = view_from_ndescs(lcols, nl, ln);
   auto right = view_from_ndescs(rcols, nr, rn);
   std::vector<cudf::size_type> lo(lon, lon + nkeys), ro(ron, ron + nkeys);
   auto lopts = generate_compression_options_distributed(left, false);
   auto ropts = generate_compression_options_distributed(right, false);
   auto result = distributed_join((join_kind)kind, left, right, lo, ro, (Communicator*)comm,
-                                 lopts, ropts, over_decom, report_timing != 0, nullptr, 1);
+                                 lopts, ropts, over_decom, report_timing != 0, nullptr, 1,
+                                 null_equality == DJ_NULL_UNEQUAL
+                                   ? cudf::null_equality::UNEQUAL
+                                   : cudf::null_equality::EQUAL);
   return result.release();
 }
 
@@ -3426,6 +3624,46 @@ int64_t dj_select_rows(const void* d_bits, int64_t nrows, int want_set, int64_t*
   int64_t h = 0;
   DJ_HIP_CALL(hipMemcpy(&h, count.p, 8, hipMemcpyDeviceToHost));
   return h;
+}
+
+int64_t dj_compact_keyed_rows(const void* d_bits, int64_t nrows, const int64_t* d_keys,
+                              int64_t* d_out_idx, int64_t* d_out_keys, int reps, double* h_ms)
+{
+  hipStream_t st = dj_rt_stream();
+  DBuf scratch(dj::select_rows_scratch_bytes(nrows)), count(8);
+  hipEvent_t e0, e1;
+  DJ_HIP_CALL(hipEventCreate(&e0));
+  DJ_HIP_CALL(hipEventCreate(&e1));
+  for (int r = 0; r < (reps > 0 ? reps : 1); r++) {
+    DJ_HIP_CALL(hipEventRecord(e0, st));
+    dj::compact_keyed_rows((const uint32_t*)d_bits, nrows, d_keys, d_out_idx, d_out_keys,
+                           count.i64(), st, scratch.p);
+    DJ_HIP_CALL(hipEventRecord(e1, st));
+    DJ_HIP_CALL(hipEventSynchronize(e1));
+    float ms = 0.f;
+    DJ_HIP_CALL(hipEventElapsedTime(&ms, e0, e1));
+    if (h_ms) h_ms[r] = ms;
+  }
+  DJ_HIP_CALL(hipEventDestroy(e0));
+  DJ_HIP_CALL(hipEventDestroy(e1));
+  int64_t h = 0;
+  DJ_HIP_CALL(hipMemcpy(&h, count.p, 8, hipMemcpyDeviceToHost));
+  return h;
+}
+
+int64_t dj_key_row_validity(const void* const* h_masks, int nmasks, int64_t nrows, void* d_out)
+{
+  hipStream_t st = dj_rt_stream();
+  DJ_CHECK_ERROR(nmasks >= 1 && nmasks <= dj::kMaxKeyMasks, "key_row_validity: 1..4 masks");
+  const uint32_t* masks[dj::kMaxKeyMasks];
+  for (int c = 0; c < nmasks; c++) masks[c] = (const uint32_t*)h_masks[c];
+  DBuf cnt(8);
+  DJ_HIP_CALL(hipMemsetAsync(cnt.p, 0, 8, st));
+  dj::key_row_validity(masks, nmasks, nrows, (uint32_t*)d_out, (unsigned long long*)cnt.p, st);
+  unsigned long long h = 0;
+  DJ_HIP_CALL(hipMemcpyAsync(&h, cnt.p, 8, hipMemcpyDeviceToHost, st));
+  DJ_HIP_CALL(hipStreamSynchronize(st));
+  return (int64_t)h;
 }
 
 int64_t dj_select_rows_tile_rows(void) { return dj::select_rows_tile_rows(); }

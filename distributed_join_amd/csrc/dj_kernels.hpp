@@ -363,6 +363,15 @@ void copy_bitmask_segments(const void* d_segments, int S, int64_t total_bits, ui
 /* *d_count (caller-zeroed) += number of 0 bits among the first n of d_mask */
 void count_unset_bits(const uint32_t* d_mask, int64_t n, unsigned long long* d_count,
                       hipStream_t s);
+/* Row validity of a key tuple: word w of d_out = the AND of word w of the
+ * nmasks (1..kMaxKeyMasks) host-listed device masks, a null pointer counting
+ * as all ones; bits at and past nrows are written as 0 whatever the sources
+ * hold there. d_out holds ceil(nrows / 32) words, each stored once.
+ * *d_null_count (caller-zeroed) += the 0 bits among the first nrows. Runs on
+ * the mask-word grid (kSpanMaskWords). */
+constexpr int kMaxKeyMasks = 4;
+void key_row_validity(const uint32_t* const* masks, int nmasks, int64_t nrows, uint32_t* d_out,
+                      unsigned long long* d_null_count, hipStream_t s);
 
 /* ----- row sets (dj_rowset.hip; same bit layout, here 1 = "row is in the
  * set"): from a join's pair list to the rows a left / semi / anti join keeps */
@@ -387,6 +396,13 @@ void mark_rows(const int64_t* d_idx, int64_t n, uint32_t* d_bits, hipStream_t s,
 size_t select_rows_scratch_bytes(int64_t nrows);
 void select_rows(const uint32_t* d_bits, int64_t nrows, bool want_set, int64_t* d_out_idx,
                  int64_t* d_count, hipStream_t s, void* d_scratch);
+/* select_rows(want_set = true) that carries a key along: d_out_idx as there,
+ * and d_out_keys[k] = d_keys[d_out_idx[k]]. d_keys holds nrows elements, both
+ * outputs as many as are selected; scratch and grid (kSpanSelectRows) are
+ * select_rows'. */
+void compact_keyed_rows(const uint32_t* d_bits, int64_t nrows, const int64_t* d_keys,
+                        int64_t* d_out_idx, int64_t* d_out_keys, int64_t* d_count,
+                        hipStream_t s, void* d_scratch);
 /* rows one block of select_rows ranks at a time (tests probe around it) */
 int64_t select_rows_tile_rows();
 
@@ -406,9 +422,11 @@ struct GridSpan {
 };
 enum {
   kSpanMaskGather = 0,   /* gather_bitmasks: rows */
-  kSpanMaskWords = 1,    /* copy_bitmask_segments, count_unset_bits: mask words */
+  kSpanMaskWords = 1,    /* copy_bitmask_segments, count_unset_bits, key_row_validity:
+                            mask words */
   kSpanMarkRows = 2,     /* mark_rows: indices */
-  kSpanSelectRows = 3,   /* select_rows: rows; scan_pass: tile_scan with chunk 1 */
+  kSpanSelectRows = 3,   /* select_rows, compact_keyed_rows: rows; scan_pass: tile_scan
+                            with chunk 1 */
   kSpanGatherFused = 4,  /* gather_table, fused kernel: rows */
   kSpanGatherColumn = 5, /* gather_table, per-column kernel: rows */
   kSpanStringRows = 6,   /* sizes_from_offsets, gather_sizes_starts,

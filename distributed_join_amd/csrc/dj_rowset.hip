@@ -7,10 +7,14 @@
  *                times, from any number of lanes, waves and blocks at once
  *   select_rows  the indices i < nrows whose bit equals want_set, ascending,
  *                and their number
+ *   compact_keyed_rows
+ *                select_rows for the set bits that also carries a key: next
+ *                to every selected row number goes keys[row]
  *
  * mark_rows is the only kernel of the library that does a read-modify-write
  * on a bitmap word: a no-return atomic OR, issued only for words that hold a
- * marked bit. select_rows builds every output element once, by rank.
+ * marked bit. select_rows and compact_keyed_rows build every output element
+ * once, by rank.
  */
 #include "dj_error.hpp"
 #include "dj_kernels.hpp"
@@ -103,7 +107,15 @@ __global__ __launch_bounds__(kRowsetBlock) void mark_rows_kernel(
  *                  and the block streams the list out as base + local, one
  *                  coalesced 8-byte-per-lane store stream per tile.
  * The bitmap is read twice (nrows / 8 bytes each time, the second time from
- * L2 at the sizes a join produces); every output element is written once. */
+ * L2 at the sizes a join produces); every output element is written once.
+ *
+ * compact_keyed_rows is the same three phases with KEYED = true in the third:
+ * the lane that stores out[base + k] = row also stores out_keys[base + k] =
+ * keys[row]. The rows of a tile ascend with k, so the key reads of a tile
+ * walk forward through one window of kTileRows * 8 = 64 KiB, and the key
+ * stores are the same coalesced stream as the index stores. Per selected row
+ * that is 8 bytes read and 16 written: nrows / 8 + 24 * selected bytes for
+ * the whole call, counting the bitmap once (its second read is L2's). */
 constexpr int kTileWords = kRowsetBlock;
 constexpr int64_t kTileRows = (int64_t)kTileWords * 32;
 
@@ -169,9 +181,11 @@ __global__ __launch_bounds__(kScanBlock) void tile_scan_kernel(int64_t* __restri
   if (threadIdx.x == kScanBlock - 1) *d_count = s_part[kScanBlock - 1];
 }
 
+template <bool KEYED>
 __global__ __launch_bounds__(kRowsetBlock) void tile_write_kernel(
   const uint32_t* __restrict__ bits, int64_t nrows, int64_t ntiles, bool want_set,
-  const int64_t* __restrict__ tile_base, int64_t* __restrict__ out)
+  const int64_t* __restrict__ tile_base, int64_t* __restrict__ out,
+  const int64_t* __restrict__ keys, int64_t* __restrict__ out_keys)
 {
   __shared__ uint16_t s_local[kTileRows];  // 16 KiB: tile-local row numbers by rank
   __shared__ uint32_t s_wave[kRowsetBlock / kWave];
@@ -202,8 +216,11 @@ __global__ __launch_bounds__(kRowsetBlock) void tile_write_kernel(
     __syncthreads();
     const int64_t base = tile_base[tile];
     const int64_t row0 = tile * kTileRows;
-    for (uint32_t k = threadIdx.x; k < total; k += kRowsetBlock)
-      out[base + k] = row0 + s_local[k];
+    for (uint32_t k = threadIdx.x; k < total; k += kRowsetBlock) {
+      const int64_t row = row0 + s_local[k];  // a set bit below nrows
+      out[base + k] = row;
+      if (KEYED) out_keys[base + k] = keys[row];
+    }
     __syncthreads();  // s_local and s_wave are reused by the next tile
   }
 }
@@ -254,6 +271,34 @@ size_t select_rows_scratch_bytes(int64_t nrows)
   return (size_t)(ntiles > 0 ? ntiles : 1) * sizeof(int64_t);
 }
 
+namespace {
+
+/* the three phases; d_keys / d_out_keys non-null selects the keyed write */
+void select_impl(const uint32_t* d_bits, int64_t nrows, bool want_set, const int64_t* d_keys,
+                 int64_t* d_out_idx, int64_t* d_out_keys, int64_t* d_count, hipStream_t s,
+                 void* d_scratch)
+{
+  const int64_t ntiles = select_tiles(nrows);
+  const int grid = (int)(ntiles < kRowsetGridCap ? ntiles : kRowsetGridCap);
+  int64_t* tiles = (int64_t*)d_scratch;
+  hipLaunchKernelGGL(tile_count_kernel, dim3(grid), dim3(kRowsetBlock), 0, s, d_bits, nrows,
+                     ntiles, want_set, tiles);
+  DJ_HIP_CALL(hipGetLastError());
+  hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, tiles, ntiles, d_count);
+  DJ_HIP_CALL(hipGetLastError());
+  if (d_keys != nullptr)
+    hipLaunchKernelGGL(tile_write_kernel<true>, dim3(grid), dim3(kRowsetBlock), 0, s, d_bits,
+                       nrows, ntiles, want_set, (const int64_t*)tiles, d_out_idx, d_keys,
+                       d_out_keys);
+  else
+    hipLaunchKernelGGL(tile_write_kernel<false>, dim3(grid), dim3(kRowsetBlock), 0, s, d_bits,
+                       nrows, ntiles, want_set, (const int64_t*)tiles, d_out_idx,
+                       (const int64_t*)nullptr, (int64_t*)nullptr);
+  DJ_HIP_CALL(hipGetLastError());
+}
+
+}  // namespace
+
 void select_rows(const uint32_t* d_bits, int64_t nrows, bool want_set, int64_t* d_out_idx,
                  int64_t* d_count, hipStream_t s, void* d_scratch)
 {
@@ -264,17 +309,22 @@ void select_rows(const uint32_t* d_bits, int64_t nrows, bool want_set, int64_t* 
   }
   DJ_CHECK_ERROR(d_bits != nullptr && d_out_idx != nullptr && d_scratch != nullptr,
                  "select_rows: null pointer");
-  const int64_t ntiles = select_tiles(nrows);
-  const int grid = (int)(ntiles < kRowsetGridCap ? ntiles : kRowsetGridCap);
-  int64_t* tiles = (int64_t*)d_scratch;
-  hipLaunchKernelGGL(tile_count_kernel, dim3(grid), dim3(kRowsetBlock), 0, s, d_bits, nrows,
-                     ntiles, want_set, tiles);
-  DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, tiles, ntiles, d_count);
-  DJ_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(tile_write_kernel, dim3(grid), dim3(kRowsetBlock), 0, s, d_bits, nrows,
-                     ntiles, want_set, (const int64_t*)tiles, d_out_idx);
-  DJ_HIP_CALL(hipGetLastError());
+  select_impl(d_bits, nrows, want_set, nullptr, d_out_idx, nullptr, d_count, s, d_scratch);
+}
+
+void compact_keyed_rows(const uint32_t* d_bits, int64_t nrows, const int64_t* d_keys,
+                        int64_t* d_out_idx, int64_t* d_out_keys, int64_t* d_count,
+                        hipStream_t s, void* d_scratch)
+{
+  DJ_CHECK_ERROR(d_count != nullptr, "compact_keyed_rows: null count pointer");
+  if (nrows <= 0) {
+    DJ_HIP_CALL(hipMemsetAsync(d_count, 0, sizeof(int64_t), s));
+    return;
+  }
+  DJ_CHECK_ERROR(d_bits != nullptr && d_keys != nullptr && d_out_idx != nullptr &&
+                   d_out_keys != nullptr && d_scratch != nullptr,
+                 "compact_keyed_rows: null pointer");
+  select_impl(d_bits, nrows, true, d_keys, d_out_idx, d_out_keys, d_count, s, d_scratch);
 }
 
 }  // namespace dj

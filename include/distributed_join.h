@@ -234,7 +234,8 @@ void dj_gather_columns(const dj_gather_desc* descs, int ncols, const int64_t* d_
  * null_count the number of null rows (0 when null_mask is NULL). Null keys
  * join with null_equality::EQUAL (null matches null and no valid key), the
  * default of the cudf::inner_join call the reference makes
- * (distributed_join.cpp:79); a null key element places on the element hash
+ * (distributed_join.cpp:79), unless an entry point takes a null_equality
+ * argument (dj_cpp_distributed_join_ncols_multi_ne below); a null key element places on the element hash
  * 0xFFFFFFFF (csrc/dj_hash.h). An output column has a mask exactly when its
  * source column had one. The *_cols entry points above stay mask-free. */
 typedef struct {
@@ -306,6 +307,19 @@ void* dj_cpp_distributed_join_ncols_multi(void* comm, int kind, const dj_ncol_de
                                           int64_t rn, const int32_t* lon, const int32_t* ron,
                                           int nkeys, int over_decom, int report_timing);
 
+/* dj_cpp_distributed_join_ncols_multi with the null equality of the key
+ * comparison after kind: DJ_NULL_EQUAL, the rule of every other entry point,
+ * or DJ_NULL_UNEQUAL, SQL's, under which a row with a null in any column of
+ * its key tuple matches nothing (include/distributed_join.hpp documents what
+ * each kind then returns). Any other value raises. */
+#define DJ_NULL_EQUAL 0
+#define DJ_NULL_UNEQUAL 1
+void* dj_cpp_distributed_join_ncols_multi_ne(void* comm, int kind, int null_equality,
+                                             const dj_ncol_desc* lcols, int nl, int64_t ln,
+                                             const dj_ncol_desc* rcols, int nr, int64_t rn,
+                                             const int32_t* lon, const int32_t* ron, int nkeys,
+                                             int over_decom, int report_timing);
+
 /* test/bench hook for the row-marking kernel: sets bit d_idx[i] (row i = bit
  * i % 32 of uint32 word i / 32) of d_bits for every i < n. The caller zeroes
  * d_bits and keeps every index inside it; an index may repeat any number of
@@ -325,6 +339,19 @@ void dj_mark_rows(const int64_t* d_idx, int64_t n, void* d_bits, int mode, int r
  * hipEvent pairs; h_ms as above. Synchronizes. */
 int64_t dj_select_rows(const void* d_bits, int64_t nrows, int want_set, int64_t* d_out_idx,
                        int reps, double* h_ms);
+/* test/bench hook for the keyed compaction: dj_select_rows with want_set = 1
+ * that also writes d_out_keys[k] = d_keys[d_out_idx[k]]. d_keys holds nrows
+ * int64, both outputs at least as many as are selected. Returns their
+ * number; reps and h_ms as above. Synchronizes. */
+int64_t dj_compact_keyed_rows(const void* d_bits, int64_t nrows, const int64_t* d_keys,
+                              int64_t* d_out_idx, int64_t* d_out_keys, int reps, double* h_ms);
+/* test/bench hook for the row validity of a key tuple: word w of d_out
+ * (ceil(nrows / 32) uint32 words, each written once) = the AND of word w of
+ * the nmasks (1..4) masks in the HOST array h_masks, a NULL entry counting
+ * as all ones; bits at and past nrows are written as 0 whatever the sources
+ * hold there. Returns the number of 0 bits among the first nrows.
+ * Synchronizes. */
+int64_t dj_key_row_validity(const void* const* h_masks, int nmasks, int64_t nrows, void* d_out);
 /* rows one block of dj_select_rows ranks at a time */
 int64_t dj_select_rows_tile_rows(void);
 
@@ -339,9 +366,11 @@ int64_t dj_select_rows_tile_rows(void);
  * constants the launchers use, so tests that size their inputs from them
  * follow a changed cap. Returns 0, or -1 for an unknown family. */
 #define DJ_SPAN_MASK_GATHER 0    /* gather_bitmasks: rows */
-#define DJ_SPAN_MASK_WORDS 1     /* copy_bitmask_segments, count_unset_bits: 32-bit words */
+#define DJ_SPAN_MASK_WORDS 1     /* copy_bitmask_segments, count_unset_bits,
+                                    key_row_validity: 32-bit words */
 #define DJ_SPAN_MARK_ROWS 2      /* mark_rows: indices */
-#define DJ_SPAN_SELECT_ROWS 3    /* select_rows: rows; scan: tile_scan with a chunk of 1 */
+#define DJ_SPAN_SELECT_ROWS 3    /* select_rows, compact_keyed_rows: rows; scan: tile_scan
+                                    with a chunk of 1 */
 #define DJ_SPAN_GATHER_FUSED 4   /* table gather, fused kernel: rows */
 #define DJ_SPAN_GATHER_COLUMN 5  /* table gather, per-column kernel: rows */
 #define DJ_SPAN_STRING_ROWS 6    /* sizes_from_offsets, gather_sizes_starts,

@@ -62,7 +62,8 @@ std::unique_ptr<cudf::table> distributed_inner_join(
  * join_kind selects what distributed_join returns on each rank; the
  * concatenation over ranks is the global result, row order unspecified:
  *
- *  INNER      exactly distributed_inner_join (the call is forwarded).
+ *  INNER      exactly distributed_inner_join (with null_equality::EQUAL the
+ *             call is forwarded).
  *  LEFT       all left columns then all right columns. Every matching pair
  *             appears as in the inner join; every left row without a match
  *             appears once with null right-hand cells. EVERY right-hand
@@ -76,9 +77,27 @@ std::unique_ptr<cudf::table> distributed_inner_join(
  *             match, each once.
  *  LEFT_ANTI  the left columns of the left rows that have no match.
  *
- * Null keys compare as in the inner join (null_equality::EQUAL): a null left
- * key is matched exactly when the right side holds a null key in the same
- * position of the tuple; values stored under a null are never looked at.
+ * Null keys, compare_nulls (the trailing argument of distributed_join and its
+ * three named siblings; distributed_inner_join keeps the reference's
+ * signature and is always EQUAL). Values stored under a null are never looked
+ * at in either mode.
+ *  null_equality::EQUAL (the default, cuDF's default and what the reference
+ *    runs): a null key element matches a null element in the same position of
+ *    the tuple and no valid one.
+ *  null_equality::UNEQUAL (SQL: NULL = NULL is not true): a row with a null in
+ *    any column of its key tuple matches nothing. Null-key right rows are in no
+ *    result. Null-key left rows are dropped by INNER and LEFT_SEMI, appear once
+ *    each with null right-hand cells in LEFT, and are kept by LEFT_ANTI. Valid
+ *    keys join as under EQUAL; without a null in any key column the two modes
+ *    give the same rows. Mask presence on output columns follows the kind's
+ *    rule above in both modes. On one rank the null-key rows stay out of the
+ *    bucket join and a single integer key does not need the fused key chain;
+ *    over several ranks each rank strips its tables to their valid-key rows
+ *    before anything is communicated (one extra gather of a table whose key
+ *    holds nulls), runs the EQUAL route on them, and appends its own null-key
+ *    left rows (LEFT, LEFT_ANTI) to its result: null-key rows never reach
+ *    the communicator. INNER under UNEQUAL is
+ *    distributed_join(join_kind::INNER, ..., null_equality::UNEQUAL).
  * An empty left table gives an empty result of the kind's schema; an empty
  * right table gives LEFT = every left row with an all-null right side,
  * LEFT_SEMI = empty, LEFT_ANTI = every left row.
@@ -106,7 +125,8 @@ std::unique_ptr<cudf::table> distributed_join(
   int over_decom_factor            = 1,
   bool report_timing               = false,
   void* preallocated_pinned_buffer = nullptr,
-  int nvlink_domain_size           = 1);
+  int nvlink_domain_size           = 1,
+  cudf::null_equality compare_nulls = cudf::null_equality::EQUAL);
 
 /* distributed_join(join_kind::LEFT, ...) */
 std::unique_ptr<cudf::table> distributed_left_join(
@@ -120,7 +140,8 @@ std::unique_ptr<cudf::table> distributed_left_join(
   int over_decom_factor            = 1,
   bool report_timing               = false,
   void* preallocated_pinned_buffer = nullptr,
-  int nvlink_domain_size           = 1);
+  int nvlink_domain_size           = 1,
+  cudf::null_equality compare_nulls = cudf::null_equality::EQUAL);
 
 /* distributed_join(join_kind::LEFT_SEMI, ...) */
 std::unique_ptr<cudf::table> distributed_left_semi_join(
@@ -134,7 +155,8 @@ std::unique_ptr<cudf::table> distributed_left_semi_join(
   int over_decom_factor            = 1,
   bool report_timing               = false,
   void* preallocated_pinned_buffer = nullptr,
-  int nvlink_domain_size           = 1);
+  int nvlink_domain_size           = 1,
+  cudf::null_equality compare_nulls = cudf::null_equality::EQUAL);
 
 /* distributed_join(join_kind::LEFT_ANTI, ...) */
 std::unique_ptr<cudf::table> distributed_left_anti_join(
@@ -148,4 +170,5 @@ std::unique_ptr<cudf::table> distributed_left_anti_join(
   int over_decom_factor            = 1,
   bool report_timing               = false,
   void* preallocated_pinned_buffer = nullptr,
-  int nvlink_domain_size           = 1);
+  int nvlink_domain_size           = 1,
+  cudf::null_equality compare_nulls = cudf::null_equality::EQUAL);

@@ -147,6 +147,11 @@ inline constexpr bool is_cascaded_supported(data_type t)
 
 /* mirrors cudf::hash_id as used by shuffle_on.hpp:49 */
 enum class hash_id : int32_t { HASH_IDENTITY = 0, HASH_MURMUR3 = 1 };
+
+/* how null key elements compare in a join (cuDF's name and order): EQUAL, a
+ * null matches a null in the same position of the key tuple; UNEQUAL, the SQL
+ * rule, a row with a null anywhere in its key tuple matches nothing */
+enum class null_equality : bool { EQUAL, UNEQUAL };
 constexpr uint32_t DEFAULT_HASH_SEED = 0;
 
 class column_view {
