@@ -413,11 +413,14 @@ struct PartGeom {
   int blocks;
 };
 
+constexpr int kPartRowsPerWave = 256;  // target; more once the wave cap binds
+constexpr int kPartWaveCap = 8192;
+
 static PartGeom part_geom(int64_t n)
 {
   PartGeom g;
-  int64_t target = (n + 255) / 256;  // >=256 rows per wave
-  g.nwaves = target < 1 ? 1 : (target > 8192 ? 8192 : target);
+  int64_t target = (n + kPartRowsPerWave - 1) / kPartRowsPerWave;
+  g.nwaves = target < 1 ? 1 : (target > kPartWaveCap ? kPartWaveCap : target);
   g.blocks = (int)((g.nwaves + WPB - 1) / WPB);
   g.nwaves = (int64_t)g.blocks * WPB;
   g.rows_per_wave = (n + g.nwaves - 1) / g.nwaves;
@@ -1939,6 +1942,14 @@ BucketPartitionShape bucket_partition_shape()
 {
   return {SCATTER_TILE, SLACK_TILE, BTILE, BUCKET_BLOCKS, BUCKET_THREADS};
 }
+
+HashPartitionShape hash_partition_shape()
+{
+  /* part_scan_kernel scans BLOCK waves per pass */
+  return {kPartRowsPerWave, kPartWaveCap, WPB, BLOCK};
+}
+
+TableJoinShape table_join_shape() { return {BLOCK, kGridCap}; }
 
 void lds_join(const longlong2* d_lrows, const int64_t* d_loff, const longlong2* d_rrows,
               const int64_t* d_roff, int B, int table_slots, int64_t* d_out0, int64_t* d_out1,

@@ -192,6 +192,21 @@ struct BucketPartitionShape {
   int scatter_tile, slack_tile, btile, bucket_blocks, bucket_threads;
 };
 BucketPartitionShape bucket_partition_shape();
+/* the stable hash partition's geometry (tests size their inputs from it): a
+ * wave takes ceil(n / nwaves) consecutive rows, nwaves = ceil(n /
+ * target_rows_per_wave) capped at wave_cap and rounded up to whole blocks of
+ * waves_per_block waves; the per-partition scan over the waves covers
+ * scan_block of them per pass. */
+struct HashPartitionShape {
+  int target_rows_per_wave, wave_cap, waves_per_block, scan_block;
+};
+HashPartitionShape hash_partition_shape();
+/* the global-table join's and neg1_cross_join's grid: block size and the cap
+ * in blocks; one trip of a kernel covers block * grid_cap rows */
+struct TableJoinShape {
+  int block, grid_cap;
+};
+TableJoinShape table_join_shape();
 /* Global-table build/probe over interleaved pair inputs (skew fallback). */
 void join_build_pairs(const longlong2* d_rows, int64_t ln, int64_t* d_table, int64_t nslots,
                       int* d_error, hipStream_t s);
