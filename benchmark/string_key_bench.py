@@ -100,14 +100,7 @@ def join_child(args):
     L.dj_memcpy_h2d(d_off, off.ctypes.data, off.nbytes)
     comm = dj.CppCommunicator(0, 1)
 
-    def pack(cols):
-        arr = (dj.ColDesc * len(cols))()
-        for i, c in enumerate(cols):
-            arr[i].type_id, arr[i].data = c[0], c[1]
-            arr[i].chars = c[2] if len(c) > 2 else None
-            arr[i].chars_bytes = c[3] if len(c) > 3 else 0
-        return arr
-
+    pack = dj._pack_cols
     legs = {
         "int64_key": (pack([(dj.TYPE_INT64, lk.ptr), (dj.TYPE_INT64, lp.ptr)]),
                       pack([(dj.TYPE_INT64, rk.ptr), (dj.TYPE_INT64, rp.ptr)])),

@@ -83,11 +83,7 @@ def make_table(keys, types):
     return cols
 
 
-def pack(cols):
-    arr = (dj.ColDesc * len(cols))()
-    for i, (t, p) in enumerate(cols):
-        arr[i].type_id, arr[i].data, arr[i].chars, arr[i].chars_bytes = t, p, None, 0
-    return arr
+pack = dj._pack_cols
 
 
 def free_table(cols):

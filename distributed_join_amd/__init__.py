@@ -428,19 +428,22 @@ class ColDesc(ctypes.Structure):
                 ("chars", ctypes.c_void_p), ("chars_bytes", ctypes.c_int64)]
 
 
+def _pack_cols(cols):
+    """cols: (type_id, data_ptr[, chars_ptr, chars_bytes]) tuples -> ColDesc array."""
+    arr = (ColDesc * len(cols))()
+    for i, c in enumerate(cols):
+        arr[i].type_id = c[0]
+        arr[i].data = c[1]
+        arr[i].chars = c[2] if len(c) > 2 else None
+        arr[i].chars_bytes = c[3] if len(c) > 3 else 0
+    return arr
+
+
 def cpp_distributed_inner_join_cols(comm, lcols, ln, rcols, rn, key_l=0, key_r=0,
                                     over_decom=1):
     """Generic join over column descriptors: each col is
     (type_id, data_ptr[, chars_ptr, chars_bytes])."""
-    def pack(cols):
-        arr = (ColDesc * len(cols))()
-        for i, c in enumerate(cols):
-            arr[i].type_id = c[0]
-            arr[i].data = c[1]
-            arr[i].chars = c[2] if len(c) > 2 else None
-            arr[i].chars_bytes = c[3] if len(c) > 3 else 0
-        return arr
-    la, ra = pack(lcols), pack(rcols)
+    la, ra = _pack_cols(lcols), _pack_cols(rcols)
     t = lib().dj_cpp_distributed_inner_join_cols(
         comm.ptr, ctypes.cast(la, ctypes.c_void_p), len(lcols), ln,
         ctypes.cast(ra, ctypes.c_void_p), len(rcols), rn, key_l, key_r, over_decom, 0)
@@ -451,15 +454,7 @@ def cpp_distributed_inner_join_cols_multi(comm, lcols, ln, rcols, rn, left_on, r
                                           over_decom=1):
     """Composite-key join over column descriptors (left_on/right_on are
     lists of key column indices; the single-key restriction lifts here)."""
-    def pack(cols):
-        arr = (ColDesc * len(cols))()
-        for i, c in enumerate(cols):
-            arr[i].type_id = c[0]
-            arr[i].data = c[1]
-            arr[i].chars = c[2] if len(c) > 2 else None
-            arr[i].chars_bytes = c[3] if len(c) > 3 else 0
-        return arr
-    la, ra = pack(lcols), pack(rcols)
+    la, ra = _pack_cols(lcols), _pack_cols(rcols)
     lon = np.asarray(left_on, dtype=np.int32)
     ron = np.asarray(right_on, dtype=np.int32)
     t = lib().dj_cpp_distributed_inner_join_cols_multi(
@@ -507,12 +502,7 @@ def cpp_shuffle_on_cols(comm, cols, n, on, hash_fn=HASH_MURMUR3, seed=0, compres
     `on` lists the key column indices, STRING columns included. compression:
     False/0 none, True/1 fixed bitpack policy, 2 sampling auto-select, 3 an
     explicit cascaded option on every column (a loud error on float/bool)."""
-    arr = (ColDesc * len(cols))()
-    for i, c in enumerate(cols):
-        arr[i].type_id = c[0]
-        arr[i].data = c[1]
-        arr[i].chars = c[2] if len(c) > 2 else None
-        arr[i].chars_bytes = c[3] if len(c) > 3 else 0
+    arr = _pack_cols(cols)
     keys = np.asarray(on, dtype=np.int32)
     t = lib().dj_cpp_shuffle_on_cols(comm.ptr, ctypes.cast(arr, ctypes.c_void_p), len(cols), n,
                                      keys.ctypes.data, len(keys), hash_fn, seed,
@@ -523,12 +513,7 @@ def cpp_shuffle_on_cols(comm, cols, n, on, hash_fn=HASH_MURMUR3, seed=0, compres
 def cpp_partition_cols(cols, n, on, nparts, hash_fn=HASH_MURMUR3, seed=0):
     """The placement step of shuffle_on alone (test hook): returns
     (numpy columns of the partitioned table, host offsets[nparts+1])."""
-    arr = (ColDesc * len(cols))()
-    for i, c in enumerate(cols):
-        arr[i].type_id = c[0]
-        arr[i].data = c[1]
-        arr[i].chars = c[2] if len(c) > 2 else None
-        arr[i].chars_bytes = c[3] if len(c) > 3 else 0
+    arr = _pack_cols(cols)
     keys = np.asarray(on, dtype=np.int32)
     offsets = np.zeros(nparts + 1, dtype=np.int64)
     t = lib().dj_cpp_partition_cols(ctypes.cast(arr, ctypes.c_void_p), len(cols), n,

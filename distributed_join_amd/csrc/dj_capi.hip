@@ -85,7 +85,7 @@ void record_end(hipStream_t s) { DJ_HIP_CALL(hipEventRecord(g_spans.back().stop,
 
 }  // namespace dj_timing
 
-/* streams shared with the C++ orchestration layer (dj_cpp_api.hip) */
+/* streams shared with the C++ orchestration layer (dj_host.hpp) */
 hipStream_t dj_rt_stream() { return stream(); }
 hipStream_t dj_rt_comm_stream() { return comm_stream(); }
 

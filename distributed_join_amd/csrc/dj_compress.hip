@@ -27,7 +27,7 @@
  *
  * Cascaded options mapping (ColumnCompressionOptions.cascaded_format):
  *   num_RLEs ∈ {0,1}, num_deltas ∈ {0,1}, use_bp ∈ {0,1}; >1 passes raise
- *   at option validation (dj_cpp_api.hip). Without use_bp the subslices
+ *   at option validation (dj_compress_opts.hip). Without use_bp the subslices
  *   pack at width 64 (the raw fallback then usually wins on-device).
  * 1-/2-/4-byte elements are sign-extended to i64 values before zigzag (they
  * pack to their natural width anyway) and truncated back to the element

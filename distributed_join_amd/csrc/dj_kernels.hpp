@@ -452,8 +452,8 @@ enum {
   kSpanCodecElems = 10,  /* codec element loops: elements; scan_pass: values of
                             scan64_exclusive */
   kSpanCodecPack = 11,   /* codec pack loops: values (32 per group) */
-  kSpanKeyHelpers = 12,  /* widen_key, narrow_key, fuse_keys, nullable_key_hash,
-                            rebase_offsets (dj_cpp_api.hip): rows */
+  kSpanKeyHelpers = 12,  /* widen_key, narrow_key, fuse_key_columns, nullable_key_hash,
+                            rebase_offsets (dj_key_helpers.hip): rows */
   kSpanFamilies = 13
 };
 GridSpan bitmask_grid_span(int family);
@@ -461,7 +461,30 @@ GridSpan rowset_grid_span(int family);
 GridSpan gather_grid_span(int family);
 GridSpan strings_grid_span(int family);
 GridSpan compress_grid_span(int family);
-GridSpan key_helper_grid_span(int family); /* dj_cpp_api.hip */
+GridSpan key_helper_grid_span(int family); /* dj_key_helpers.hip */
+
+/* ----- key helper kernels (dj_key_helpers.hip): a thread per row, grid
+ * kSpanKeyHelpers. Enqueue only; n >= 0 rows ----- */
+/* d_dst[i] = i / = value */
+void iota_i64(int64_t* d_dst, int64_t n, hipStream_t s);
+void fill_i32(int32_t* d_dst, int64_t n, int32_t value, hipStream_t s);
+/* integer-rep key column of kind kKey* <-> the engine's int64 key:
+ * d_dst[i] = load_key_i64(d_src, kind, i); back by truncation to `width`
+ * (1, 2 or 4) bytes */
+void widen_key(const void* d_src, int kind, int64_t n, int64_t* d_dst, hipStream_t s);
+void narrow_key(const int64_t* d_src, int64_t n, int width, void* d_dst, hipStream_t s);
+/* d_out[i] = the dj_mix64 chain over row i of ncols (<= 4) key columns; kinds
+ * holds 4 bits of kKey* per column, d_masks[c] (nullptr = all valid) makes a
+ * null element enter as kNullKeyHash; weak != 0 keeps 4 bits of the hash */
+void fuse_key_columns(const int64_t* const d_cols[4], const uint32_t* const d_masks[4],
+                      uint32_t kinds, int ncols, int64_t n, int weak, int64_t* d_out,
+                      hipStream_t s);
+/* d_out[i] = dj_row_hash of a valid element of a nullable key column,
+ * kNullKeyHash of a null one */
+void nullable_key_hash(const void* d_src, int kind, const uint32_t* d_valid, int64_t n,
+                       int hash_fn, uint32_t seed, int64_t* d_out, hipStream_t s);
+/* d_dst[i] = d_src[i] + base (STRING offsets of a concatenated part) */
+void rebase_offsets(const int32_t* d_src, int64_t n, int32_t base, int32_t* d_dst, hipStream_t s);
 
 /* ----- small utilities ----- */
 void fill_i64(int64_t* d_dst, int64_t value, int64_t n, hipStream_t s);

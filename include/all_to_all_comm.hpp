@@ -168,7 +168,7 @@ class AllToAllCommunicator {
   /* strings machinery (reference all_to_all_comm.hpp:349-360: per string
    * column the char-offset boundaries per peer, plus device buffers of row
    * sizes to send / received — sizes, not offsets, go on the wire). Opaque
-   * here; defined in dj_cpp_api.hip. */
+   * here; defined in dj_all_to_all.hip. */
   struct StringsState;
   std::shared_ptr<StringsState> strings;
   friend struct AllToAllCommunicatorAccess;

@@ -253,7 +253,10 @@ void* dj_cpp_distributed_inner_join_ncols_multi(void* comm, const dj_ncol_desc* 
                                                 int64_t rn, const int32_t* lon,
                                                 const int32_t* ron, int nkeys, int over_decom,
                                                 int report_timing);
-/* dj_cpp_shuffle_on_cols over nullable descriptors */
+/* dj_cpp_shuffle_on_cols over nullable descriptors. The two share one body,
+ * so `compression` means here what it means there: 0 none, 1 the fixed
+ * bitpack policy, 2 sampling auto-select, 3 an explicit cascaded option on
+ * every column (2 and 3 used to act as 1 on this entry point). */
 void* dj_cpp_shuffle_on_ncols(void* comm, const dj_ncol_desc* cols, int nc, int64_t n,
                               const int32_t* on, int nkeys, int hash_function, uint32_t seed,
                               int compression);

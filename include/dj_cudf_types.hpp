@@ -261,7 +261,7 @@ class mutable_column_view {
   size_type _null_count{0};
 };
 
-/* owning device column (HIP device memory; allocation in dj_cpp_api.hip) */
+/* owning device column (HIP device memory; allocation in dj_cudf_shim.hip) */
 class column {
  public:
   column(data_type type, size_type size);            // allocates device memory

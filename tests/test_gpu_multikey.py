@@ -1,8 +1,8 @@
 """Composite (multi-column) join keys through the drop-in path.
 
 The engine joins on a fused hash chain of the key tuple and filters
-fused-hash collisions against the real columns (dj_cpp_api.hip
-local_inner_join) — reference semantics: cudf::inner_join on
+fused-hash collisions against the real columns (dj_local_join.hip
+local_join) — reference semantics: cudf::inner_join on
 arbitrary left_on/right_on (distributed_join.cpp:71-132). Parity oracle:
 the single-key CPU join on a collision-free combined key
 (k0 * 2^32 + k1, exact in int64 for the test ranges).

@@ -515,7 +515,8 @@ def test_codec_pack_second_trip_int8(dj, deltas):
 
 # ------------------------- 6. engine helper kernels, end to end at world size 1
 #
-# What runs where at one rank (csrc/dj_cpp_api.hip, local_join / place_rows):
+# What runs where at one rank (csrc/dj_local_join.hip local_join,
+# csrc/dj_table_ops.hip place_rows; the kernels: csrc/dj_key_helpers.hip):
 #   composite or nullable keys  fuse_keys, the tuple filter over the pair list
 #   one mask-free narrow key    widen_key on both inputs, narrow_key on the output
 #   left join                   mark_rows, select_rows, the null-padded gathers
