@@ -1299,7 +1299,30 @@ void subpart_lists(const int64_t* d_keys, const int64_t* d_pay, const int64_t* d
  * ~2.35 ms (profiles/r02_join_factorial.log; the goto-drain structure below
  * measured 1.40 ms). Only KBUK == 4 is instantiated; the KBUK == 1 branches
  * in the body (flush every bucket, the r1 behavior, ~0.3 ms slower per
- * 100 M rows) fold away. */
+ * 100 M rows) fold away.
+ *
+ * Row prefetch: each lane's first build row AND first probe row of a bucket
+ * are loaded into registers before the table clear, so both HBM misses fly
+ * over the clear and the probe row's also over the build (the r2 kernel
+ * loaded the build row after the clear and the probe row after the build,
+ * each waited for on the spot: two misses in series per bucket; 1.43 ->
+ * 1.28 ms, profiles/r03_join_prefetch.md). Predicates: lane t loads row
+ * start + t of a side only if t < that side's length — never a row outside
+ * [start, start + len), whose slack is uninitialised and, with a small
+ * capacity, another bucket's or past the buffer — and lengths/offsets only at
+ * b < B (b + 1 <= B for offsets). The rows of a bucket that is then skipped
+ * (empty side, skew) are dropped. Rows at t + blockDim.x and beyond are loaded
+ * in the loops as before. The bucket after this one is NOT prefetched, and
+ * lengths are not loaded ahead: both were built and measured (same file) and
+ * gave nothing over this — with two blocks per CU the other block's LDS work
+ * already covers what is left of the miss.
+ *
+ * SGPR budget: 80 at most, the compiler's own count included (78 slack, 74
+ * compact now). At 84-90 the kernel still reports 8 waves/SIMD but the CU
+ * takes ONE block, not two: 2.0-2.5 ms measured for otherwise identical code
+ * (same file) — very likely what the "codegen cliff" above was. Check
+ * -Rpass-analysis=kernel-resource-usage after any edit; the k loop stays
+ * rolled (unrolled x4 the compact variant carries ~100 SGPRs). */
 template <int SLOTS2, bool SLACK, int KBUK>
 __global__ __launch_bounds__(BUCKET_THREADS) void lds_join_kernel(
   const longlong2* __restrict__ lrows, const int64_t* __restrict__ loff,
@@ -1321,12 +1344,20 @@ __global__ __launch_bounds__(BUCKET_THREADS) void lds_join_kernel(
   if (threadIdx.x == 0) *cur_sh = 0;
   __syncthreads();
 
+  /* this lane's first row of [s, e), if it has one */
+  auto first_row = [&](const longlong2* __restrict__ rows, int64_t s, int64_t e) {
+    longlong2 row = {0, 0};
+    if (s + threadIdx.x < e) row = rows[s + threadIdx.x];
+    return row;
+  };
+
   for (int bb = blockIdx.x * KBUK; bb < B; bb += gridDim.x * KBUK) {
     /* Exit-clean guarantee: every group's k == KBUK-1 slot flushes — valid
      * buckets flush unconditionally there, and invalid slots (empty side,
      * skew-routed, or caller-padded zero-length buckets) jump to the flush
      * block instead of skipping it, so a block never exits carrying staged
      * rows. */
+#pragma unroll 1
     for (int k = 0; k < KBUK; k++) {
       const int b = bb + k;
       if (b >= B) break;  // dead when KBUK > 1 (padded B); real for KBUK == 1
@@ -1342,6 +1373,9 @@ __global__ __launch_bounds__(BUCKET_THREADS) void lds_join_kernel(
         r0 = roff[b];
         r1 = roff[b + 1];
       }
+      /* both sides' first rows fly over the table clear (and are dropped if
+       * the bucket is skipped below) */
+      const longlong2 lrow = first_row(lrows, l0, l1), prow = first_row(rrows, r0, r1);
       const int64_t lnb = l1 - l0;
       if (lnb == 0 || r1 == r0) {  // empty side (incl. padding buckets)
         /* KBUK == 1 flushes every valid bucket, so there is never a carry
@@ -1360,50 +1394,67 @@ __global__ __launch_bounds__(BUCKET_THREADS) void lds_join_kernel(
       for (int s = threadIdx.x; s < SLOTS2; s += blockDim.x) tbl[s].x = kEmptyKey;
       __syncthreads();
       /* build */
-      for (int64_t i = l0 + threadIdx.x; i < l1; i += blockDim.x) {
-        longlong2 row = lrows[i];
-        if (row.x == kEmptyKey) {
-          *error = 1;
-          continue;
+      {
+        longlong2 row = lrow;
+        for (int64_t i = l0 + threadIdx.x; i < l1;) {
+          if (row.x == kEmptyKey) {
+            *error = 1;
+          } else {
+            uint32_t slot = (uint32_t)dj_mix64((uint64_t)row.x) & smask;
+            for (;;) {
+              unsigned long long old = atomicCAS((unsigned long long*)&tbl[slot].x,
+                                                 (unsigned long long)kEmptyKey,
+                                                 (unsigned long long)row.x);
+              if (old == (unsigned long long)kEmptyKey) break;
+              slot = (slot + 1) & smask;
+            }
+            tbl[slot].y = row.y;
+          }
+          /* rows past the block size (buckets longer than the block): plain
+           * loads, waited for here — the empty asm is a use, so the wait sits
+           * at this load and not ahead of the first row's insert */
+          i += blockDim.x;
+          if (i < l1) {
+            row = lrows[i];
+            asm volatile("" ::"v"(row.x));
+          }
         }
-        uint32_t slot = (uint32_t)dj_mix64((uint64_t)row.x) & smask;
-        for (;;) {
-          unsigned long long old = atomicCAS((unsigned long long*)&tbl[slot].x,
-                                             (unsigned long long)kEmptyKey,
-                                             (unsigned long long)row.x);
-          if (old == (unsigned long long)kEmptyKey) break;
-          slot = (slot + 1) & smask;
-        }
-        tbl[slot].y = row.y;
       }
       __syncthreads();
       /* single-pass probe: matches append to the LDS stage */
-      for (int64_t j = r0 + threadIdx.x; j < r1; j += blockDim.x) {
-        longlong2 prow = rrows[j];
-        uint32_t slot = (uint32_t)dj_mix64((uint64_t)prow.x) & smask;
-        for (;;) {
-          longlong2 e = tbl[slot];
-          if (e.x == kEmptyKey) break;
-          if (e.x == prow.x) {
-            uint32_t pos = atomicAdd(cur_sh, 1u);
-            if (pos < (uint32_t)S) {
-              stage[0 * S + pos] = prow.x;
-              stage[1 * S + pos] = e.y;
-              stage[2 * S + pos] = prow.x;
-              stage[3 * S + pos] = prow.y;
-            } else {
-              /* stage overflow (heavy duplication): spill directly; the
-               * compiler wave-aggregates the counter atomic */
-              long long idx = (long long)atomicAdd(counter, 1ull);
-              if (idx < cap) {
-                out0[idx] = prow.x;
-                out1[idx] = e.y;
-                out2[idx] = prow.x;
-                out3[idx] = prow.y;
+      {
+        longlong2 prw = prow;
+        for (int64_t j = r0 + threadIdx.x; j < r1;) {
+          uint32_t slot = (uint32_t)dj_mix64((uint64_t)prw.x) & smask;
+          for (;;) {
+            longlong2 e = tbl[slot];
+            if (e.x == kEmptyKey) break;
+            if (e.x == prw.x) {
+              uint32_t pos = atomicAdd(cur_sh, 1u);
+              if (pos < (uint32_t)S) {
+                stage[0 * S + pos] = prw.x;
+                stage[1 * S + pos] = e.y;
+                stage[2 * S + pos] = prw.x;
+                stage[3 * S + pos] = prw.y;
+              } else {
+                /* stage overflow (heavy duplication): spill directly; the
+                 * compiler wave-aggregates the counter atomic */
+                long long idx = (long long)atomicAdd(counter, 1ull);
+                if (idx < cap) {
+                  out0[idx] = prw.x;
+                  out1[idx] = e.y;
+                  out2[idx] = prw.x;
+                  out3[idx] = prw.y;
+                }
               }
             }
+            slot = (slot + 1) & smask;
           }
-          slot = (slot + 1) & smask;
+          j += blockDim.x;
+          if (j < r1) {
+            prw = rrows[j];
+            asm volatile("" ::"v"(prw.x));
+          }
         }
       }
     flush:
